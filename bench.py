@@ -17,9 +17,13 @@ every step's results are in HBM.  Output: ONE JSON line on rank 0.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     ... bench.py --mode strong      # BASELINE configs[3] as written: ONE 8M-ray batch cut into N contiguous shards
     ... bench.py --scene city-synth | soup-synth | --scene-file some.bin      # another scene class / a reference-format scene file (Renderer/main.cpp:117-191)
-The line also carries (tools/bench_extras.py): `roofline` (the measured roof: the CU gather path on this cache-resident scene, HBM on
-battlefield-synth-XL), `cpu_baseline`, and — at any N — the same K steps with the RCCL all-gather of every step's hit records, serialised
-and overlapped (`with_allgather_of_results[_overlapped]`).
+    ... bench.py --dump-outputs DIR # the hit records of the last timed step as DIR/{triangle,t,u,v}.npy (dump_outputs below)
+A plain run does only what the headline figure needs: set-up, the warm-up (`pre_timed_launches` single launches that bring the clocks up,
+then W steps), the K timed steps, the line (`roofline` and `cpu_baseline` are null).  With --full the line also carries
+(tools/bench_extras.py): `roofline` (the measured roof: the CU gather path on this cache-resident scene, HBM on battlefield-synth-XL; its
+kernel duration is that of the single launches), the oracle check of every timed record and `cpu_baseline`, the other configs, and — at
+any N — the same K steps with the RCCL all-gather of every step's hit records, serialised and overlapped
+(`with_allgather_of_results[_overlapped]`).
 """
 import argparse
 import gc
@@ -110,6 +114,25 @@ def usable_cores():
     return n
 
 
+DUMP_MAX_ROWS = 1 << 21        # 28 bytes per dumped record (sample_index included): 56 MiB at most
+DUMP_SEED = 0x0D5EED
+
+
+def dump_outputs(directory, records):
+    """--dump-outputs: the Result records ([n, 4] float32 on the device: primId bits, t, u, v — miss colour where primId is 0xFFFFFFFF) the
+    last timed step left in its result array, as the caller of racc_hip_intersect_device receives them: triangle.npy (the uint32 ids as
+    float64, exact), t.npy, u.npy, v.npy (float32).  Beyond DUMP_MAX_ROWS records (--mode strong at few GPUs) a fixed, seeded sample of the
+    rows, whose indices are sample_index.npy (float64)."""
+    import numpy as np
+    rec = records.cpu().numpy()
+    os.makedirs(directory, exist_ok=True)
+    if len(rec) > DUMP_MAX_ROWS:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(len(rec), DUMP_MAX_ROWS, replace=False))
+        rec = rec[idx]
+        np.save(os.path.join(directory, "sample_index.npy"), idx.astype("<f8"))
+    np.save(os.path.join(directory, "triangle.npy"), rec[:, 0].view("<u4").astype("<f8"))
+    for col, name in enumerate(("t", "u", "v"), 1):
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(rec[:, col]))
 
 
 def main():
@@ -119,10 +142,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--mode", choices=("weak", "strong"), default="weak",
                     help="weak (default): 1M rays per GPU per step; strong: one 8M-ray batch per step cut into N shards (configs[3])")
-    ap.add_argument("--no-gather", action="store_true", help="skip the all-gather figures (`with_allgather_of_results[_overlapped]`); RACC_BENCH_NO_GATHER=1 does the same")
-    ap.add_argument("--gather", action="store_true", help="the all-gather figures even with --no-extras (they are part of the default line since round 6)")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the oracle check and the CPU legs (profiling runs)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the untimed extra measurements (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: `roofline`, the oracle check of every timed record and "
+                         "`cpu_baseline`, the all-gather figures, the other configs (tools/bench_extras.py).  Off by default: a plain run sets up, warms up, times "
+                         "the K steps and prints the line.  The four options below choose among these parts and mean nothing without --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the hit records of the last one (rank 0's) as DIR/triangle.npy, t.npy, u.npy, v.npy (dump_outputs)")
+    ap.add_argument("--no-gather", action="store_true", help="with --full: skip the all-gather figures (`with_allgather_of_results[_overlapped]`); RACC_BENCH_NO_GATHER=1 does the same")
+    ap.add_argument("--gather", action="store_true", help="with --full: the all-gather figures even with --no-extras (they are part of the --full line since round 6)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the oracle check and the CPU legs")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the untimed extra measurements")
     ap.add_argument("--workload", choices=("diffuse", "coherent", "xl", "xl_diffuse"), default="diffuse",
                     help="diffuse (default, the headline): 1M first-bounce diffuse rays per step (configs[2]); coherent: the 1M primary rays (configs[1]); "
                          "xl / xl_diffuse: battlefield-synth-XL (25 M triangles, 1.5 GB on the device: past the Infinity Cache) with 1M incoherent rays / "
@@ -259,6 +288,9 @@ def main():
     # of the last 30 (the duration settles only after the GPU has been busy for ~15 ms), first re-tracing one batch, then rotating through the
     # sample sets as the timed steps and the committed rocprofv3 passes do.  Reported as `pre_timed_launches` (RACC_BENCH_ISO_LAUNCHES=0 skips
     # them — the profiling passes do, so that their last K traversal dispatches are the K steps).
+    # A plain run issues the same launches and reports no duration (that is --full's `roofline`): they are also what brings the clocks up
+    # before the warm-up steps, and `value` is defined on a GPU in that state — without them the same command measured 4,437 instead of
+    # 4,946 Mrays/s at 20 steps and 5,257 instead of 5,360 at 200 (two runs each, one MI355X); they take 40 ms.
     # No collector pause inside the K steps or between the warm-up and them: a full collection of this process takes ~35 ms, during
     # which the GPU would sit idle and drop its clocks.  Collected here, once; switched back on after the timed region.
     gc.collect()
@@ -288,7 +320,9 @@ def main():
     barrier()
     gc.enable()
     kernel_ms = drain_kernel_times()            # HIP events around each traversal kernel, on the stream it ran on
-    for k in range(len(d_sets), min(args.steps, len(outs))):      # step k traced sample set k mod NSETS: same rays, same bits (the sets themselves are held to the oracle below)
+    if args.dump_outputs and rank == 0:      # before anything else writes into the result arrays
+        dump_outputs(args.dump_outputs, outs[(args.steps - 1) % len(outs)])
+    for k in range(len(d_sets), min(args.steps, len(outs)) if args.full else 0):      # step k traced sample set k mod NSETS: same rays, same bits (the sets themselves are held to the oracle below)
         if not torch.equal(outs[k].view(torch.int32), outs[k % len(d_sets)].view(torch.int32)):
             sys.exit("bench: step %d of the timed region produced other results than step %d (same rays)" % (k, k % len(d_sets)))
 
@@ -336,8 +370,8 @@ def main():
         full=full, xl_run=xl_run, standard_scene=standard_scene, elapsed=elapsed, iso_ms=iso_ms, iso_same_ms=iso_same_ms, iso_n=iso_n, kernel_ms=kernel_ms,
         usable_cores=usable_cores, committed_profile=committed_profile, steady_state_profile=steady_state_profile, gather_ceiling=gather_ceiling,
         profile_dir=PROFILE_DIR, kernel_name=KERNEL_NAME, golden={},
-        d_ref_bits=outs[0].view(torch.int32).clone(),      # the default kernel's records of the timed batch (the extras reuse the result arrays)
-        set_bits=[outs[k].view(torch.int32).clone() for k in range(1, min(len(d_sets), args.steps, len(outs)))])      # ... and of the other sample sets
+        d_ref_bits=outs[0].view(torch.int32).clone() if args.full else None,      # the default kernel's records of the timed batch (the extras reuse the result arrays)
+        set_bits=[outs[k].view(torch.int32).clone() for k in range(1, min(len(d_sets), args.steps, len(outs)) if args.full else 0)])      # ... and of the other sample sets
 
     scene_label = ("battlefield-synth-XL" if xl_run else sc["name"].split("(")[0]) + (" (stand-in; reference scene unavailable)" if not args.scene_file else "") + ", %d triangles, " % len(sc["indices"])
     if args.workload == "xl":
@@ -370,9 +404,9 @@ def main():
         "collective_backend": (backend if world > 1 else None), "rccl_ranks": (comm_ranks if (world > 1 and backend == "nccl") else None), "comm_ranks": comm_ranks,
     }
 
-    # ---- extras, all outside the timed region (tools/bench_extras.py) ----------------------------
+    # ---- extras, all outside the timed region and with --full only (tools/bench_extras.py) -------
     extras = {}
-    want_gather = (args.gather or not (args.no_gather or args.no_extras or os.environ.get("RACC_BENCH_NO_GATHER"))) and (backend == "nccl" or world == 1) and not xl_run
+    want_gather = args.full and (args.gather or not (args.no_gather or args.no_extras or os.environ.get("RACC_BENCH_NO_GATHER"))) and (backend == "nccl" or world == 1) and not xl_run
     if want_gather:
         # The same K steps with the all-gather of every step's hit records, serialised and overlapped.  A collective on every
         # rank: under a watchdog of its own at N > 1 — if the C-ABI's RCCL instance does not come up on some rank, rank 0 still prints the line
@@ -405,14 +439,14 @@ def main():
         os.dup2(real_stdout, 1)
         os.close(real_stdout)
     # (N > 1: no other untimed extras — rank 0 would still be measuring while the other ranks tear the process group down)
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         extras.update(bx.single_gpu_extras(S))
     xl = None
-    if rank == 0 and world == 1 and full and standard_scene and args.mode == "weak" and args.workload == "diffuse" and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and full and standard_scene and args.mode == "weak" and args.workload == "diffuse" and not args.no_extras:
         xl = bx.xl_rooflines(S)
 
-    # ---- oracle check, roofline + CPU baseline (rank 0) -----------------------------------------
-    if rank == 0:
+    # ---- oracle check, roofline + CPU baseline (rank 0, --full) ---------------------------------
+    if rank == 0 and args.full:
         alg_bytes, alg_by_set, src = None, None, None
         try:
             with open(os.path.join(ROOT, "tests", "golden", "algorithmic_bytes.json")) as f:
@@ -430,6 +464,7 @@ def main():
             alg_bytes, src = (S.golden.get(golden_key) or {}).get("bytes"), "tests/golden/algorithmic_bytes.json"
         line["roofline"] = bx.build_roofline(S, alg_bytes, alg_by_set, src, extras, xl)
         line.update(extras)
+    if rank == 0:
         print(json.dumps(line), flush=True)
 
     scene.destroy()
