@@ -253,6 +253,24 @@ int racc_hip_intersect_device(racc_hip_ctx* ctx, const racc_hip_scene* scene, co
 int racc_hip_intersect_device_timed(racc_hip_ctx* ctx, const racc_hip_scene* scene, const racc_hip_env* env,
                                     const void* d_rays, void* d_results, uint32_t count,
                                     uint32_t lane, uint32_t iters, float* ms);
+/* ---- occlusion (any-hit) queries ----
+ * ≙ nothing in the reference (its scheduler knows the closest hit only); Embree's rtcOccluded is the usual counterpart.  The shadow /
+ * visibility ray: is anything in (minT, maxT]?  The answer is exactly "racc_hip_intersect* would report a hit for this ray" — the same
+ * traversal rule with the ray's own maxT and the same pair test in the same arithmetic — but the traversal stops at the first accepted
+ * triangle pair, keeps no hit state, gathers no remap entry, samples no environment (hence no `env` argument) and writes one byte
+ * per ray instead of a 16-byte Result.  Rays the closest-hit path rejects (non-finite origin, direction or minT, NaN maxT) give 0.
+ * Its own kernel (occludedKernel, rayaccel_amd/csrc/racc_occlusion.inc) on the BVH2 records every scene carries, whatever
+ * kernel_variant the context was created with.  No lane, chain, group or RCCL involvement: a launch owns its scratch memory (one
+ * cursor word + stack spill, allocated and freed in stream order around the kernel), so launches on different streams overlap each
+ * other and the chained closest-hit batches of racc_hip_intersect_device, and racc_hip_destroy leaves nothing of them behind.
+ *
+ * occluded[i] = 1 if anything lies in (minT, maxT] of rays[i], else 0.  Device-resident, asynchronous on `stream`
+ * (hipStream_t as void*, NULL = the default stream, as racc_hip_memcpy_d2d_async); complete after racc_hip_stream_synchronize,
+ * which also reports a watchdog trip.  ctx is checked first, then scene; count == 0 is a successful no-op. */
+int racc_hip_occluded_device(racc_hip_ctx*, const racc_hip_scene*, const void* d_rays, uint8_t* d_occluded, uint32_t count, void* stream);
+/* Host arrays, blocking, callable from several threads at once (every call brings its own stream and staging arrays). */
+int racc_hip_occluded(racc_hip_ctx*, const racc_hip_scene*, const void* rays, uint8_t* occluded, uint32_t count);
+
 int racc_hip_get_launch_info(racc_hip_ctx* ctx, uint32_t lane, racc_hip_launch_info* info);
 /* With racc_hip_options::time_kernels: durations (ms, HIP events on the stream each launch went to) of the lane's traversal
  * kernels since the last call, oldest first, at most `capacity` (the engine keeps the last 256); *n = how many.  Waits for them. */

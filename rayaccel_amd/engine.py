@@ -82,6 +82,8 @@ ABI = {
     "racc_hip_intersect_streams_async": (_i, [_vp, _vp, _vp, _u32, _P(_vp), _P(_vp), _P(_u32), _u32]),
     "racc_hip_intersect_device": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp]),
     "racc_hip_intersect_device_timed": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _P(C.c_float)]),
+    "racc_hip_occluded_device": (_i, [_vp, _vp, _vp, _vp, _u32, _vp]),
+    "racc_hip_occluded": (_i, [_vp, _vp, _vp, _vp, _u32]),
     "racc_hip_get_launch_info": (_i, [_vp, _u32, _P(LaunchInfo)]),
     "racc_hip_read_kernel_times": (_i, [_vp, _u32, _P(C.c_float), _u32, _P(_u32)]),
     "racc_hip_read_stats": (_i, [_vp, _u32, _P(_u64), _i]),
@@ -417,6 +419,22 @@ class Context:
         ms = (C.c_float * iters)()
         _check(load_library().racc_hip_intersect_device_timed(self._h, scene._h, env._h if env else None, d_rays, d_results, count, lane, iters, ms))
         return list(ms)
+
+    # -- occlusion (any-hit) ---------------------------------------------------------------
+    def occluded(self, scene, rays, out=None):
+        """Host Ray[N] in, np.uint8[N] out (1 = something lies in (minT, maxT]), blocking (racc_hip_occluded; no reference counterpart)."""
+        rays = np.ascontiguousarray(rays)
+        assert rays.dtype.itemsize == 32
+        if out is None:
+            out = np.zeros(len(rays), np.uint8)
+        assert out.dtype == np.uint8 and out.flags.c_contiguous and len(out) >= len(rays)
+        _check(load_library().racc_hip_occluded(self._h, scene._h, _ptr(rays), _ptr(out), len(rays)))
+        return out
+
+    def occluded_device(self, scene, d_rays, d_out, count, stream=None):
+        """Device-resident form (racc_hip_occluded_device): asynchronous on `stream` (None = the default stream), complete after
+        stream_synchronize(stream)."""
+        _check(load_library().racc_hip_occluded_device(self._h, scene._h, d_rays, d_out, count, stream))
 
     def wait(self, lane=0):
         _check(load_library().racc_hip_wait(self._h, lane))
