@@ -126,6 +126,13 @@ ContextInfo info(Context* context);                      // reference :105
 // Copies its inputs (reference Scene.cpp:203-207,342-346).  vertices 16-byte aligned, indexCount % 3 == 0.
 Scene* createScene(Context* context, const Vertex* vertices, unsigned vertexCount, const uint32_t* indices, unsigned indexCount);
 void destroy(Scene* scene);                              // reference :109
+// Extension (no counterpart in the reference, whose scenes are frozen at createScene): refits the scene to moved vertices — the same
+// vertexCount and the index list createScene was given (createScene keeps a copy of it: 12 B of host memory per triangle).  The tree keeps
+// its topology; triangle pairs and boxes are recomputed on every GPU of the context (racc_hip_scene_refit, racc_hip.h).  Called from the
+// application thread between two render() calls; blocks.  On failure — a context in fast-traversal mode included: its compressed tree is
+// not refitted — returns false after one "RayAccelerator: ..." line on stderr, and the scene is as it was before the call if the failure
+// was found before any GPU was touched (a wrong count, a coordinate that is not finite, fast-traversal mode).
+bool updateScene(Scene* scene, const Vertex* vertices, unsigned vertexCount);
 
 Environment* createEnvironment(Context* context, const Color* colors, unsigned width, unsigned height);   // reference :111
 void destroy(Environment* environment);                  // reference :113

@@ -271,6 +271,41 @@ int racc_hip_occluded_device(racc_hip_ctx*, const racc_hip_scene*, const void* d
 /* Host arrays, blocking, callable from several threads at once (every call brings its own stream and staging arrays). */
 int racc_hip_occluded(racc_hip_ctx*, const racc_hip_scene*, const void* rays, uint8_t* occluded, uint32_t count);
 
+/* ---- dynamic scenes: refit of a device-resident scene to moved vertices ----
+ * ≙ nothing in the reference (its scenes are frozen at createScene, Scene.cpp:216-349); Embree's rtcCommitScene on a deformable scene and
+ * every GPU API's BVH update are the usual counterparts.  The topology stays (child references, leaf ranges, remap, the device node order,
+ * hence inner_height, max_leaf_pairs and every count in racc_hip_scene_info); the 48 B pair records and the child boxes of the 64 B node
+ * records are recomputed by the rule of racc_host_blobs_refit (below, "host refit"), bit for bit.  A refitted tree traces the moved mesh
+ * correctly; how well it traces it depends on how far the vertices moved from the positions the tree was built for.
+ *
+ * All refit state lives in the racc_hip_refit handle: the four vertex indices of every pair, every device record's parent, the list of
+ * leaf references, one arrival counter per record (device memory), the blob's topology words (host memory, 16 B per inner node, kept
+ * from racc_hip_scene_upload on) and the map from blob order to device order.  Destroy the handle before its scene.
+ * That table of topology words is the one cost refit puts on callers who never use it: racc_hip_scene_upload keeps it for every scene (the
+ * device drops the blob's node order and its kind / parent words, so they cannot be recovered later); RACC_REFIT_TOPOLOGY=0 in the
+ * environment switches it off, and racc_hip_refit_create then refuses.  The unpadded pair count is taken to be where the last leaf ends (as in
+ * every blob the builder makes); records behind it are padding, rewritten as copies of pair 0.
+ * racc_hip_refit_create: indices / index_count as the scene was built from, vertex_count = the length of every vertex array to come.
+ * Validates like the host refit (remap's triangle ids < index_count / 3, every index < vertex_count).  RACC_HIP_ERR_INVALID, scene
+ * untouched, when the scene carries a 4-wide, compressed or SoA copy of the tree — a context created with kernel_variant 45 or 50,
+ * wide_below != 0 or the SoA variant: those copies are not refitted and a stale one would give wrong hits — or is a device group's replica.
+ *
+ * Ordering contract: a refit rewrites arrays that traversal kernels read.
+ *   racc_hip_scene_refit (host xyzw vertices, validated: finite) calls racc_hip_synchronize(ctx) first, so that no kernel of a chain is
+ *   alive, then runs on a stream of the handle's own and has completed when it returns.
+ *   racc_hip_scene_refit_device (device xyzw vertices, NOT validated: they must be finite) is asynchronous on `stream` (hipStream_t as
+ *   void*, NULL = the default stream).  Before the call the caller guarantees that every batch and occlusion launch issued on this scene
+ *   has been waited for; afterwards the caller calls racc_hip_stream_synchronize on that stream before the next launch on the scene.
+ * racc_hip_refit_download: the scene's current records back in reference format and blob order (what racc_hip_scene_upload was given,
+ * boxes and pair records as the last completed refit left them); either pointer may be NULL; capacities in records (node_count /
+ * padded pair_count of racc_hip_scene_info).  The caller has waited for the refit. */
+typedef struct racc_hip_refit racc_hip_refit;
+int racc_hip_refit_create(racc_hip_ctx*, racc_hip_scene*, const uint32_t* indices, uint32_t index_count, uint32_t vertex_count, racc_hip_refit** out);
+int racc_hip_refit_destroy(racc_hip_ctx*, racc_hip_refit*);
+int racc_hip_scene_refit(racc_hip_ctx*, racc_hip_refit*, const float* vertices, uint32_t vertex_count);
+int racc_hip_scene_refit_device(racc_hip_ctx*, racc_hip_refit*, const void* d_vertices, uint32_t vertex_count, void* stream);
+int racc_hip_refit_download(racc_hip_ctx*, racc_hip_refit*, void* nodes64_out, uint32_t node_capacity, void* pairs48_out, uint32_t pair_capacity);
+
 int racc_hip_get_launch_info(racc_hip_ctx* ctx, uint32_t lane, racc_hip_launch_info* info);
 /* With racc_hip_options::time_kernels: durations (ms, HIP events on the stream each launch went to) of the lane's traversal
  * kernels since the last call, oldest first, at most `capacity` (the engine keeps the last 256); *n = how many.  Waits for them. */
@@ -398,6 +433,25 @@ int racc_host_scene_blobs(const racc_host_scene* scene,
 int racc_host_scene_bvh2(const racc_host_scene* scene,
                          const void** nodes48, uint32_t* node_count,
                          const uint32_t** triangles, uint32_t* triangle_count);
+
+/* Host refit: reference-format blobs in, the same blobs for moved vertices out (pure function: no GPU, no scene handle; outputs may alias
+ * inputs).  kind, parent, first, last and remap are unchanged.  The rule — the specification racc_hip_scene_refit reproduces bit for bit:
+ *   pair record  remap[2p] = t0 | ea << 30, remap[2p+1] = t1 | (eb+1) << 30 or 0 for a lone triangle (then p3 = p1); with a / b the index
+ *                triples of t0 / t1 the pair's vertices are a[ea], a[(ea+1)%3], a[(ea+2)%3], b[(eb+2)%3]; the record is e1 = p0 - p1,
+ *                e2 = p2 - p0, e3 = p3 - p0, p0 (Scene.cpp:149-153); records [pair_count, pair_count_padded) are copies of the new pair 0
+ *   select       min = b < acc ? b : acc, max = b > acc ? b : acc per component (not fmin / fmax: -0.0 against +0.0)
+ *   leaf box     the select folded over the leaf's pairs first .. first+cnt-1, each pair's vertices in order p0 p1 p2 p3, from p0 of the first
+ *   inner box    the node's first-child box (accumulator) with its last-child box, by the same select
+ * Refitting a tree the builder made to the vertices it was built from reproduces it byte for byte unless it has spatial splits (the library
+ * default): there a split reference's clipped box becomes its whole pair's box (every refit box contains the built one).
+ * RACC_HIP_ERR_INVALID before any output byte is written: a blob racc_hip_scene_upload would refuse, a triangle id in remap[0, 2 * pair_count)
+ * >= index_count / 3, an index >= vertex_count, a vertex coordinate (x, y, z) that is not finite. */
+int racc_host_blobs_refit(const void* nodes64, uint32_t node_count,
+                          const void* pairs48, uint32_t pair_count_padded, uint32_t pair_count,
+                          const uint32_t* remap, uint32_t remap_count,
+                          const float* vertices /* xyzw */, uint32_t vertex_count,
+                          const uint32_t* indices, uint32_t index_count,
+                          void* nodes64_out, void* pairs48_out);
 
 /* The device layout racc_hip_scene_upload gives the node blob (for tools and tests; needs no GPU).  Device record, 64 B: words 0-1 =
  * the two child references (re-numbered), words 2-3 unused, then the child boxes as six (min, max) plane pairs: Lx Ly Lz Rx Ry Rz.

@@ -30,6 +30,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <new>
 #include <thread>
 #include <vector>
 
@@ -46,7 +47,10 @@ struct GpuContextTag {
 
 struct Scene {
     Context* context;
-    std::vector<racc_hip_scene*> devices;     // one replica per GPU of the context (the scene is read-only: Scene.cpp:342-346)
+    std::vector<racc_hip_scene*> devices;     // one replica per GPU of the context (read-only while a frame renders: Scene.cpp:342-346)
+    std::vector<uint32_t> indices;            // the index list createScene was given (12 B per triangle): updateScene's refit handles need it
+    unsigned vertexCount = 0;
+    std::vector<racc_hip_refit*> refits;      // one per replica, created by the first updateScene
 };
 
 struct Environment {
@@ -480,8 +484,10 @@ Scene* createScene(Context* c, const Vertex* vertices, unsigned vertexCount, con
     const uint32_t* remap = nullptr;
     uint32_t nNodes = 0, nPairsPadded = 0, nPairs = 0, nRemap = 0;
     racc_host_scene_blobs(host, &nodes, &nNodes, &pairs, &nPairsPadded, &nPairs, &remap, &nRemap);
-    Scene* s = new (std::nothrow) Scene{c, {}};
+    Scene* s = new (std::nothrow) Scene{c, {}, {}, vertexCount, {}};
     if (!s) { racc_host_scene_free(host); complain("Unable to allocate memory."); return nullptr; }
+    try { s->indices.assign(indices, indices + indexCount); }      // updateScene's refit handles need the index list
+    catch (const std::bad_alloc&) { racc_host_scene_free(host); delete s; complain("Unable to allocate memory."); return nullptr; }
     for (racc_hip_ctx* hip : c->hips) {          // one replica per GPU
         racc_hip_scene* dev = nullptr;
         if (racc_hip_scene_upload(hip, nodes, nNodes, pairs, nPairsPadded, remap, nRemap, &dev) != RACC_HIP_OK) {
@@ -498,8 +504,32 @@ Scene* createScene(Context* c, const Vertex* vertices, unsigned vertexCount, con
 
 void destroy(Scene* s) {   // reference Scene.cpp:359-372
     if (!s) return;
+    for (size_t d = 0; d < s->refits.size(); ++d) racc_hip_refit_destroy(s->context->hips[d], s->refits[d]);
     for (size_t d = 0; d < s->devices.size(); ++d) racc_hip_scene_free(s->context->hips[d], s->devices[d]);
     delete s;
+}
+
+// No counterpart in the reference (its scenes are frozen at createScene).  Called from the application thread between two render() calls:
+// no frame is in flight, and every replica is refitted with the blocking entry, which has completed when it returns.
+bool updateScene(Scene* s, const Vertex* vertices, unsigned vertexCount) {
+    if (!s || !vertices) { complain("updateScene: null argument."); return false; }
+    if (vertexCount != s->vertexCount) { complain("updateScene: the vertex count differs from createScene's."); return false; }
+    Context* c = s->context;
+    while (s->refits.size() < s->devices.size()) {      // first call: one refit handle per GPU
+        const size_t d = s->refits.size();
+        racc_hip_refit* refit = nullptr;
+        if (racc_hip_refit_create(c->hips[d], s->devices[d], s->indices.data(), uint32_t(s->indices.size()), vertexCount, &refit) != RACC_HIP_OK) {
+            complainHip("updateScene: cannot prepare the scene for refitting");      // (a context in fast-traversal mode among the reasons)
+            return false;
+        }
+        s->refits.push_back(refit);
+    }
+    for (size_t d = 0; d < s->devices.size(); ++d)
+        if (racc_hip_scene_refit(c->hips[d], s->refits[d], &vertices->x, vertexCount) != RACC_HIP_OK) {
+            complainHip("updateScene: refit failed");
+            return false;
+        }
+    return true;
 }
 
 Environment* createEnvironment(Context* c, const Color* colors, unsigned width, unsigned height) {

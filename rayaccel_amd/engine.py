@@ -84,6 +84,11 @@ ABI = {
     "racc_hip_intersect_device_timed": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _P(C.c_float)]),
     "racc_hip_occluded_device": (_i, [_vp, _vp, _vp, _vp, _u32, _vp]),
     "racc_hip_occluded": (_i, [_vp, _vp, _vp, _vp, _u32]),
+    "racc_hip_refit_create": (_i, [_vp, _vp, _vp, _u32, _u32, _P(_vp)]),
+    "racc_hip_refit_destroy": (_i, [_vp, _vp]),
+    "racc_hip_scene_refit": (_i, [_vp, _vp, _vp, _u32]),
+    "racc_hip_scene_refit_device": (_i, [_vp, _vp, _vp, _u32, _vp]),
+    "racc_hip_refit_download": (_i, [_vp, _vp, _vp, _u32, _vp, _u32]),
     "racc_hip_get_launch_info": (_i, [_vp, _u32, _P(LaunchInfo)]),
     "racc_hip_read_kernel_times": (_i, [_vp, _u32, _P(C.c_float), _u32, _P(_u32)]),
     "racc_hip_read_stats": (_i, [_vp, _u32, _P(_u64), _i]),
@@ -116,6 +121,7 @@ ABI = {
     "racc_host_scene_free": (_i, [_vp]),
     "racc_host_scene_blobs": (_i, [_vp, _P(_vp), _P(_u32), _P(_vp), _P(_u32), _P(_u32), _P(_vp), _P(_u32)]),
     "racc_host_scene_bvh2": (_i, [_vp, _P(_vp), _P(_u32), _P(_vp), _P(_u32)]),
+    "racc_host_blobs_refit": (_i, [_vp, _u32, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _vp]),
     "racc_host_scene_device_nodes": (_i, [_vp, _u32, _u32, _u32, _i, _vp, _u32, _P(_u32)]),
 }
 
@@ -257,6 +263,49 @@ def device_nodes(nodes, pair_count, remap_count, order=1):
     return out
 
 
+def host_refit(blobs, vertices, indices):
+    """racc_host_blobs_refit: the reference-format blobs dict(nodes, pairs, remap, pair_count) refitted to `vertices` ([V,3] or [V,4]); the
+    topology (and remap) stay, pair records and child boxes are recomputed.  No GPU needed.  Returns a new blobs dict."""
+    nodes, pairs = np.ascontiguousarray(blobs["nodes"]), np.ascontiguousarray(blobs["pairs"])
+    remap = np.ascontiguousarray(blobs["remap"], dtype=np.uint32)
+    assert nodes.dtype.itemsize == 64 and pairs.dtype.itemsize == 48
+    v = _as_verts4(vertices)
+    idx = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+    out_nodes, out_pairs = np.zeros_like(nodes), np.zeros_like(pairs)
+    _check(load_library().racc_host_blobs_refit(_ptr(nodes), len(nodes), _ptr(pairs), len(pairs), int(blobs["pair_count"]), _ptr(remap), len(remap),
+                                                _ptr(v), len(v), _ptr(idx), idx.size, _ptr(out_nodes), _ptr(out_pairs)))
+    return dict(nodes=out_nodes, pairs=out_pairs, remap=remap.copy(), pair_count=int(blobs["pair_count"]))
+
+
+class Refit:
+    """racc_hip_refit: what it takes to refit one device-resident scene to moved vertices (Context.create_refit).  Destroy it before its scene."""
+
+    def __init__(self, ctx, scene, handle, vertex_count):
+        self._ctx, self._scene, self._h, self.vertex_count = ctx, scene, handle, int(vertex_count)
+
+    def refit(self, vertices):
+        """Host vertices ([V,3] or [V,4]), blocking (racc_hip_scene_refit): waits for everything the context has in flight first."""
+        v = _as_verts4(vertices)
+        _check(load_library().racc_hip_scene_refit(self._ctx._h, self._h, _ptr(v), len(v)))
+
+    def refit_device(self, d_vertices, vertex_count, stream=None):
+        """Device-resident xyzw vertices, asynchronous on `stream` (racc_hip_scene_refit_device): nothing issued on the scene may be in
+        flight, and stream_synchronize(stream) comes before the next launch on it."""
+        _check(load_library().racc_hip_scene_refit_device(self._ctx._h, self._h, d_vertices, vertex_count, stream))
+
+    def download(self):
+        """(nodes, pairs): the scene's current records in reference format and blob order (racc_hip_refit_download)."""
+        info = self._scene.info
+        nodes, pairs = np.zeros(info["node_count"], GPU_NODE_DTYPE), np.zeros(info["pair_count"], PAIR_DTYPE)
+        _check(load_library().racc_hip_refit_download(self._ctx._h, self._h, _ptr(nodes), len(nodes), _ptr(pairs), len(pairs)))
+        return nodes, pairs
+
+    def destroy(self):
+        if self._h:
+            load_library().racc_hip_refit_destroy(self._ctx._h, self._h)
+            self._h = None
+
+
 class Scene:
     def __init__(self, ctx, handle):
         self._ctx, self._h = ctx, handle
@@ -362,6 +411,13 @@ class Context:
         """≙ racc::createScene (RayAccelerator.h:107): host build with the library's default options, then upload."""
         hs = HostScene(vertices, indices, quality=None)
         return self.upload_scene(hs.nodes, hs.pairs, hs.remap)
+
+    def create_refit(self, scene, indices, vertex_count):
+        """racc_hip_refit_create: `indices` as the scene was built from, `vertex_count` = the length of every vertex array to come."""
+        idx = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+        h = C.c_void_p()
+        _check(load_library().racc_hip_refit_create(self._h, scene._h, _ptr(idx), idx.size, int(vertex_count), C.byref(h)))
+        return Refit(self, scene, h, vertex_count)
 
     def create_environment(self, colors):
         """≙ racc::createEnvironment (RayAccelerator.h:111); colors [H,W,4] float32."""
