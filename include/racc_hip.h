@@ -306,6 +306,57 @@ int racc_hip_scene_refit(racc_hip_ctx*, racc_hip_refit*, const float* vertices, 
 int racc_hip_scene_refit_device(racc_hip_ctx*, racc_hip_refit*, const void* d_vertices, uint32_t vertex_count, void* stream);
 int racc_hip_refit_download(racc_hip_ctx*, racc_hip_refit*, void* nodes64_out, uint32_t node_capacity, void* pairs48_out, uint32_t pair_capacity);
 
+/* ---- instancing: two-level scenes with per-instance transforms ----
+ * ≙ nothing in the reference (one flattened scene per racc::Scene, Scene.cpp:216-349); Embree's RTC_GEOMETRY_TYPE_INSTANCE and the
+ * top-level / bottom-level structures of every GPU ray-tracing API are the usual counterparts.  Uploaded scenes are the bottom level; a
+ * WORLD is an ordered list of `count` instances, each a 3x4 row-major object-to-world transform (twelve floats, rows of {a0 a1 a2 b}) and a
+ * racc_hip_scene of the same context; several instances may name one scene.  Rigid motion costs racc_hip_world_update (no rebuild, the
+ * bottom-level tree keeps its quality); a thousand copies of a mesh cost one scene plus 148 bytes each.
+ *
+ * Semantics.  inv = the inverse transform evaluated in double precision, every coefficient rounded to float once (racc_host_world_prepare
+ * returns it).  Instance i sees the ray o' = inv (o, 1), d' = inv (d, 0), each component the plain float expression
+ * ((m0 x + m1 y) + m2 z) + m3 (d': without m3), left to right, nothing fused, with the ray's own minT and maxT; the direction is not
+ * normalised, so t means the same in both spaces.  Its result h_i is exactly what racc_hip_intersect* reports for that ray on that scene
+ * (the oracle's traversal bit for bit: the reference's visiting order inside the bottom level, hence its tie behaviour).  The world result
+ * is the h_i of smallest t, exact ties to the lowest instance index: Result = its triangle, t, u, v unchanged (triangle ids are the
+ * scene's own), plus one uint32 instance index per ray.  A miss is triangle = 0xFFFFFFFF, t = u = v = 0, instance = 0xFFFFFFFF: there is no
+ * environment argument.  Rays the closest-hit path rejects (non-finite origin, direction or minT, NaN maxT — in world space or after the
+ * transform) miss.  Instances are culled by the best t so far against conservative world-space boxes (rayaccel_amd/csrc/world_build.cpp
+ * has the bound); an instance's traversal always starts with the ray's own maxT, as defined.
+ * Its own kernel (worldIntersectKernel, rayaccel_amd/csrc/racc_world.inc) on the BVH2 records every scene carries, whatever kernel_variant
+ * the context was created with.  No lane, chain, group or RCCL involvement: a launch owns its scratch memory, allocated and freed in stream
+ * order around the kernel, so launches overlap each other and chained closest-hit batches, and racc_hip_destroy leaves nothing behind.
+ *
+ * Ownership: a world BORROWS its scenes — destroy the world before freeing any of them.  racc_hip_world_create refuses (RACC_HIP_ERR_INVALID)
+ * a scene that was not uploaded through racc_hip_scene_upload on `ctx` (another context's, a device group's replica), count == 0,
+ * count > RACC_HIP_WORLD_MAX_INSTANCES and whatever racc_host_world_prepare refuses.
+ * racc_hip_world_update: new transforms for the same scenes, `count` = the world's.  Also the call to make after a member scene was
+ * refitted (racc_hip_scene_refit*): it re-reads the scenes' root boxes.  Blocking; calls racc_hip_synchronize first, as racc_hip_scene_refit
+ * does.  A refused transform leaves the world as it was.
+ * racc_hip_world_intersect_device: device-resident Ray[count] in, Result[count] and uint32[count] out, asynchronous on `stream`
+ * (hipStream_t as void*, NULL = the default stream); complete after racc_hip_stream_synchronize, which also reports a watchdog trip.
+ * ctx is checked first, then world; count == 0 is a successful no-op.
+ * racc_hip_world_intersect: host arrays, blocking, callable from several threads at once (every call brings its own stream and staging).
+ * Out of scope: an instanced occlusion query, environment sampling on a miss, racc::render carrying instance ids (its Result has no room),
+ * device groups, the 4-wide kernels, multi-level instancing (an instance of a world). */
+#define RACC_HIP_WORLD_MAX_INSTANCES (1u << 20)
+typedef struct racc_hip_world racc_hip_world;
+typedef struct racc_hip_world_info {
+    uint32_t instance_count;
+    uint32_t node_count;           /* top-level inner nodes */
+    uint32_t height;               /* levels of top-level inner nodes on the longest root path */
+    uint32_t lds_levels;           /* top-level stack levels the kernel keeps in LDS */
+    uint32_t spill_levels;         /* top-level stack levels beyond those (global memory) */
+    uint32_t bottom_spill_levels;  /* bottom-level stack levels beyond the kernel's LDS-resident ones, over all member scenes */
+    uint64_t device_bytes;         /* top-level nodes, instance order, inverse transforms, instance table — not the scenes */
+} racc_hip_world_info;
+int racc_hip_world_create(racc_hip_ctx*, const float* transforms12, const racc_hip_scene* const* scenes, uint32_t count, racc_hip_world** out);
+int racc_hip_world_update(racc_hip_ctx*, racc_hip_world*, const float* transforms12, uint32_t count);
+int racc_hip_world_destroy(racc_hip_ctx*, racc_hip_world*);
+int racc_hip_world_get_info(const racc_hip_world*, racc_hip_world_info* info);
+int racc_hip_world_intersect_device(racc_hip_ctx*, const racc_hip_world*, const void* d_rays, void* d_results, uint32_t* d_instances, uint32_t count, void* stream);
+int racc_hip_world_intersect(racc_hip_ctx*, const racc_hip_world*, const void* rays, void* results, uint32_t* instances, uint32_t count);
+
 int racc_hip_get_launch_info(racc_hip_ctx* ctx, uint32_t lane, racc_hip_launch_info* info);
 /* With racc_hip_options::time_kernels: durations (ms, HIP events on the stream each launch went to) of the lane's traversal
  * kernels since the last call, oldest first, at most `capacity` (the engine keeps the last 256); *n = how many.  Waits for them. */
@@ -452,6 +503,28 @@ int racc_host_blobs_refit(const void* nodes64, uint32_t node_count,
                           const float* vertices /* xyzw */, uint32_t vertex_count,
                           const uint32_t* indices, uint32_t index_count,
                           void* nodes64_out, void* pairs48_out);
+
+/* Host side of instancing (racc_hip_world_* above; pure function, no GPU, no handle) — ≙ nothing in the reference.  Inputs: `count`
+ * 3x4 row-major object-to-world transforms and each instance's object-space root box {min[3], max[3]} (the union of the two child boxes
+ * of its scene's root node).  Outputs, all caller-allocated and written only when the call succeeds:
+ *   inv12_out         [count][12]  the inverse transforms: evaluated in double (adjugate over determinant, translation -(A^-1 b)), each
+ *                                  coefficient rounded to float once — part of the specification of racc_hip_world_intersect*
+ *   world_boxes6_out  [count][6]   one conservative world-space box {min[3], max[3]} per instance: contains the eight transformed corners
+ *                                  of the root box, plus the instance's share of the margin that makes culling against it lossless
+ *   ray_pad_out       the ray's share of that margin: the kernel widens every box by *ray_pad_out * (|ox| + |oy| + |oz|) on every side
+ *   nodes64_out       top-level BVH2 over those boxes in the scenes' 64-byte node format (Scene.cpp:73-78), node 0 the root,
+ *                     max(count - 1, 1) nodes (node_capacity must be at least that; *node_count_out says how many were written); a leaf
+ *                     reference first | cnt << 24 names the instances order_out[first .. first + cnt) — here always one; a world of one
+ *                     instance has the empty reference 0 as its root's last child
+ *   order_out         [count]      a permutation of the instance indices
+ *   height_out        levels of inner nodes on the longest root path
+ * Deterministic (median splits of the box centres, ties by instance index).  RACC_HIP_ERR_INVALID: a NULL pointer, count == 0,
+ * count > RACC_HIP_WORLD_MAX_INSTANCES, a coefficient or box coordinate that is not finite, a box with min > max, a singular transform (its
+ * double-precision determinant is zero or not finite, or a coefficient of the inverse or of a world box is not finite in float). */
+int racc_host_world_prepare(const float* transforms12, const float* root_boxes6, uint32_t count,
+                            float* inv12_out, float* world_boxes6_out, float* ray_pad_out,
+                            void* nodes64_out, uint32_t node_capacity, uint32_t* node_count_out,
+                            uint32_t* order_out, uint32_t* height_out);
 
 /* The device layout racc_hip_scene_upload gives the node blob (for tools and tests; needs no GPU).  Device record, 64 B: words 0-1 =
  * the two child references (re-numbered), words 2-3 unused, then the child boxes as six (min, max) plane pairs: Lx Ly Lz Rx Ry Rz.

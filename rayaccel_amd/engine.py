@@ -50,6 +50,12 @@ class SceneInfo(C.Structure):
                 ("device_bytes", C.c_uint64)]
 
 
+class WorldInfo(C.Structure):
+    """racc_hip_world_info (include/racc_hip.h)."""
+    _fields_ = [("instance_count", C.c_uint32), ("node_count", C.c_uint32), ("height", C.c_uint32), ("lds_levels", C.c_uint32),
+                ("spill_levels", C.c_uint32), ("bottom_spill_levels", C.c_uint32), ("device_bytes", C.c_uint64)]
+
+
 class LaunchInfo(C.Structure):
     _fields_ = [("grid_blocks", C.c_uint32), ("block_threads", C.c_uint32), ("lds_bytes_per_block", C.c_uint32),
                 ("waves_per_simd", C.c_uint32), ("last_kernel_ms", C.c_float)]
@@ -89,6 +95,12 @@ ABI = {
     "racc_hip_scene_refit": (_i, [_vp, _vp, _vp, _u32]),
     "racc_hip_scene_refit_device": (_i, [_vp, _vp, _vp, _u32, _vp]),
     "racc_hip_refit_download": (_i, [_vp, _vp, _vp, _u32, _vp, _u32]),
+    "racc_hip_world_create": (_i, [_vp, _vp, _P(_vp), _u32, _P(_vp)]),
+    "racc_hip_world_update": (_i, [_vp, _vp, _vp, _u32]),
+    "racc_hip_world_destroy": (_i, [_vp, _vp]),
+    "racc_hip_world_get_info": (_i, [_vp, _P(WorldInfo)]),
+    "racc_hip_world_intersect_device": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _vp]),
+    "racc_hip_world_intersect": (_i, [_vp, _vp, _vp, _vp, _vp, _u32]),
     "racc_hip_get_launch_info": (_i, [_vp, _u32, _P(LaunchInfo)]),
     "racc_hip_read_kernel_times": (_i, [_vp, _u32, _P(C.c_float), _u32, _P(_u32)]),
     "racc_hip_read_stats": (_i, [_vp, _u32, _P(_u64), _i]),
@@ -122,6 +134,7 @@ ABI = {
     "racc_host_scene_blobs": (_i, [_vp, _P(_vp), _P(_u32), _P(_vp), _P(_u32), _P(_u32), _P(_vp), _P(_u32)]),
     "racc_host_scene_bvh2": (_i, [_vp, _P(_vp), _P(_u32), _P(_vp), _P(_u32)]),
     "racc_host_blobs_refit": (_i, [_vp, _u32, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _vp]),
+    "racc_host_world_prepare": (_i, [_vp, _vp, _u32, _vp, _vp, _P(C.c_float), _vp, _u32, _P(_u32), _vp, _P(_u32)]),
     "racc_host_scene_device_nodes": (_i, [_vp, _u32, _u32, _u32, _i, _vp, _u32, _P(_u32)]),
 }
 
@@ -277,6 +290,85 @@ def host_refit(blobs, vertices, indices):
     return dict(nodes=out_nodes, pairs=out_pairs, remap=remap.copy(), pair_count=int(blobs["pair_count"]))
 
 
+NO_INSTANCE = 0xFFFFFFFF      # the instance index of a miss (racc_hip_world_intersect*)
+WORLD_MAX_INSTANCES = 1 << 20      # RACC_HIP_WORLD_MAX_INSTANCES
+
+
+def _as_transforms(transforms):
+    t = np.ascontiguousarray(transforms, dtype=np.float32)
+    if t.ndim == 3 and t.shape[1:] == (3, 4):
+        t = t.reshape(len(t), 12)
+    if t.ndim != 2 or t.shape[1] != 12:
+        raise ValueError("transforms must be [N,3,4] or [N,12] float32 (row-major object-to-world)")
+    return np.ascontiguousarray(t)
+
+
+def root_box(nodes):
+    """{min[3], max[3]} of a scene's root: the union of the two child boxes of node 0 of its reference-format node blob."""
+    n = nodes[0]
+    return np.concatenate([np.minimum(n["leftMin"], n["rightMin"]), np.maximum(n["leftMax"], n["rightMax"])]).astype(np.float32)
+
+
+def host_world_prepare(transforms, root_boxes):
+    """racc_host_world_prepare: the host side of instancing (no GPU needed).  `transforms` [N,3,4] object-to-world, `root_boxes` [N,6]
+    object-space {min, max} (root_box()).  Returns dict(inv [N,3,4], world_boxes [N,6], ray_pad, nodes (top-level BVH2, GPU_NODE_DTYPE),
+    order [N], height)."""
+    t = _as_transforms(transforms)
+    rb = np.ascontiguousarray(root_boxes, dtype=np.float32).reshape(-1, 6)
+    if len(rb) != len(t):
+        raise ValueError("one root box per transform")
+    n = len(t)
+    cap = max(n - 1, 1)
+    inv, boxes = np.zeros((n, 12), np.float32), np.zeros((n, 6), np.float32)
+    nodes, order = np.zeros(cap, GPU_NODE_DTYPE), np.zeros(max(n, 1), np.uint32)
+    pad, nn, height = C.c_float(0), C.c_uint32(0), C.c_uint32(0)
+    _check(load_library().racc_host_world_prepare(_ptr(t), _ptr(rb), n, _ptr(inv), _ptr(boxes), C.byref(pad), _ptr(nodes), cap, C.byref(nn),
+                                                  _ptr(order), C.byref(height)))
+    return dict(inv=inv.reshape(n, 3, 4), world_boxes=boxes, ray_pad=float(pad.value), nodes=nodes[:nn.value].copy(), order=order[:n], height=int(height.value))
+
+
+class World:
+    """racc_hip_world: an ordered list of (object-to-world transform, Scene) instances (Context.create_world; no reference counterpart).
+    It borrows its scenes: destroy it before any of them."""
+
+    def __init__(self, ctx, handle, scenes):
+        self._ctx, self._h, self._scenes = ctx, handle, list(scenes)
+
+    @property
+    def info(self):
+        info = WorldInfo()
+        _check(load_library().racc_hip_world_get_info(self._h, C.byref(info)))
+        return {f: getattr(info, f) for f, _ in WorldInfo._fields_}
+
+    def intersect(self, rays, results=None, instances=None):
+        """Host Ray[N] in; (Result[N], uint32 instance index [N], NO_INSTANCE on a miss) out, blocking (racc_hip_world_intersect)."""
+        rays = np.ascontiguousarray(rays)
+        assert rays.dtype.itemsize == 32
+        if results is None:
+            results = np.zeros(len(rays), RESULT_DTYPE)
+        if instances is None:
+            instances = np.zeros(len(rays), np.uint32)
+        assert results.dtype.itemsize == 16 and instances.dtype == np.uint32 and results.flags.c_contiguous and instances.flags.c_contiguous
+        assert len(results) >= len(rays) and len(instances) >= len(rays)
+        _check(load_library().racc_hip_world_intersect(self._ctx._h, self._h, _ptr(rays), _ptr(results), _ptr(instances), len(rays)))
+        return results, instances
+
+    def intersect_device(self, d_rays, d_results, d_instances, count, stream=None):
+        """Device-resident form (racc_hip_world_intersect_device): asynchronous on `stream` (None = the default stream), complete after
+        Context.stream_synchronize(stream)."""
+        _check(load_library().racc_hip_world_intersect_device(self._ctx._h, self._h, d_rays, d_results, d_instances, count, stream))
+
+    def update(self, transforms):
+        """New transforms for the same scenes — also the call to make after a member scene was refitted.  Blocking (racc_hip_world_update)."""
+        t = _as_transforms(transforms)
+        _check(load_library().racc_hip_world_update(self._ctx._h, self._h, _ptr(t), len(t)))
+
+    def destroy(self):
+        if self._h:
+            load_library().racc_hip_world_destroy(self._ctx._h, self._h)
+            self._h = None
+
+
 class Refit:
     """racc_hip_refit: what it takes to refit one device-resident scene to moved vertices (Context.create_refit).  Destroy it before its scene."""
 
@@ -418,6 +510,16 @@ class Context:
         h = C.c_void_p()
         _check(load_library().racc_hip_refit_create(self._h, scene._h, _ptr(idx), idx.size, int(vertex_count), C.byref(h)))
         return Refit(self, scene, h, vertex_count)
+
+    def create_world(self, instances):
+        """racc_hip_world_create: `instances` = a sequence of (transform [3,4] object-to-world, Scene) in instance-index order."""
+        instances = list(instances)
+        scenes = [s for _, s in instances]
+        t = _as_transforms(np.array([np.asarray(m, np.float32).reshape(12) for m, _ in instances], np.float32).reshape(-1, 12))
+        arr = (C.c_void_p * max(len(scenes), 1))(*[s._h.value if isinstance(s._h, C.c_void_p) else s._h for s in scenes])
+        h = C.c_void_p()
+        _check(load_library().racc_hip_world_create(self._h, _ptr(t), arr, len(scenes), C.byref(h)))
+        return World(self, h, scenes)
 
     def create_environment(self, colors):
         """≙ racc::createEnvironment (RayAccelerator.h:111); colors [H,W,4] float32."""
