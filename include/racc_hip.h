@@ -281,9 +281,9 @@ int racc_hip_occluded(racc_hip_ctx*, const racc_hip_scene*, const void* rays, ui
  * All refit state lives in the racc_hip_refit handle: the four vertex indices of every pair, every device record's parent, the list of
  * leaf references, one arrival counter per record (device memory), the blob's topology words (host memory, 16 B per inner node, kept
  * from racc_hip_scene_upload on) and the map from blob order to device order.  Destroy the handle before its scene.
- * That table of topology words is the one cost refit puts on callers who never use it: racc_hip_scene_upload keeps it for every scene (the
- * device drops the blob's node order and its kind / parent words, so they cannot be recovered later); RACC_REFIT_TOPOLOGY=0 in the
- * environment switches it off, and racc_hip_refit_create then refuses.  The unpadded pair count is taken to be where the last leaf ends (as in
+ * Those topology words are the one cost refit puts on callers who never use it: racc_hip_scene_upload keeps them for every scene, in the
+ * record it registers per scene (the device drops the blob's node order and its kind / parent words, so they cannot be recovered later);
+ * RACC_REFIT_TOPOLOGY=0 in the environment switches that off, and racc_hip_refit_create then refuses.  The unpadded pair count is taken to be where the last leaf ends (as in
  * every blob the builder makes); records behind it are padding, rewritten as copies of pair 0.
  * racc_hip_refit_create: indices / index_count as the scene was built from, vertex_count = the length of every vertex array to come.
  * Validates like the host refit (remap's triangle ids < index_count / 3, every index < vertex_count).  RACC_HIP_ERR_INVALID, scene

@@ -1,19 +1,16 @@
 // racc_refit.inc — refit of a device-resident scene to moved vertices: refitPairsKernel, refitBoxesKernel and the C-ABI entries around
-// them (racc_hip_refit_*, racc_hip_scene_refit*).  Textually included by racc_hip_unit.hip BEHIND racc_hip.hip and racc_occlusion.inc,
-// so it sees the context, the scene's device pointers and fail() / HIP_TRY, and changes none of them.  The reference has no such
-// operation (its scenes are frozen at createScene); Embree's rtcCommitScene on a deformable scene is the usual counterpart.
+// them (racc_hip_refit_*, racc_hip_scene_refit*).  Textually included by racc_hip_unit.hip BEHIND racc_hip.hip and
+// racc_scene_registry.inc, so it sees the context, the scene's device pointers and kept topology and fail() / HIP_TRY, and changes none of
+// them.  The reference has no such operation (its scenes are frozen at createScene); Embree's rtcCommitScene on a deformable scene is the
+// usual counterpart.
 //
 // The rule is racc_host_blobs_refit's (scene_refit.cpp), reproduced bit for bit: topology unchanged, pair records re-packed from the
 // pair's four vertices, a leaf's box folded with `b < acc ? b : acc` / `b > acc ? b : acc` over its pairs' vertices in order, an inner
 // box the union of the first child's box (accumulator) with the last child's.
 //
-// All refit state lives in the racc_hip_refit handle.  What a handle needs and the device does not hold — a device record keeps only
-// the two child references of its blob node, in an order of the upload's own choosing — is the blob's topology words (kind, parent,
-// first, last: 16 B of host memory per inner node).  racc_hip_unit.hip therefore compiles racc_hip.hip's racc_hip_scene_upload /
-// racc_hip_scene_free under other names, and the public entries here wrap them: upload keeps a copy of those words in a table keyed by
-// the scene handle, free drops it.  racc_hip_scene itself gets no field.  This is a cost on EVERY upload, refitted or not — 16 B of host
-// memory per inner node and replica (battlefield-synth: 17 MB) — which RACC_REFIT_TOPOLOGY=0 switches off for a process that never refits.  (Scenes of a device group are uploaded by racc_group.inc
-// inside racc_hip.hip, i.e. without that table: racc_hip_refit_create refuses them.)
+// All refit state lives in the racc_hip_refit handle.  What a handle needs and the device does not hold is the blob's topology words,
+// which the scene registry keeps from the upload (racc_scene_registry.inc: sceneTopology; a scene without them is refused).  The handle
+// shares them, so they outlive the scene's free.
 //
 // Box step: one thread per leaf reference.  It folds its leaf's box from the vertices, writes the six planes of its side into the
 // parent's device record and climbs: an agent-scope acq_rel fetch_add on the parent's arrival counter; the first arriver retires, the
@@ -86,17 +83,6 @@ __global__ void __launch_bounds__(kRefitBlock) refitBoxesKernel(const float4* __
     }
 }
 
-// blob topology words of every scene uploaded through racc_hip_scene_upload, keyed by the scene handle (see the head of this file)
-struct RefitTopology { std::vector<uint32_t> words; uint32_t nodeCount = 0; };      // 4 per node: kind, parent, first, last
-std::mutex g_refitTopologyMutex;
-std::vector<std::pair<const racc_hip_scene*, std::shared_ptr<const RefitTopology>>> g_refitTopology;
-
-std::shared_ptr<const RefitTopology> refitTopologyOf(const racc_hip_scene* scene) {
-    std::lock_guard<std::mutex> g(g_refitTopologyMutex);
-    for (const auto& e : g_refitTopology) if (e.first == scene) return e.second;
-    return nullptr;
-}
-
 }  // namespace
 
 struct racc_hip_refit {
@@ -130,34 +116,6 @@ int refitLaunch(racc_hip_refit* r, const float4* dVertices, hipStream_t st) {
 
 extern "C" {
 
-int racc_hip_scene_upload(racc_hip_ctx* ctx, const void* nodes64, uint32_t node_count, const void* pairs48, uint32_t pair_count,
-                          const uint32_t* remap, uint32_t remap_count, racc_hip_scene** out) {
-    if (int rc = raccSceneUploadBase(ctx, nodes64, node_count, pairs48, pair_count, remap, remap_count, out)) return rc;
-    // RACC_REFIT_TOPOLOGY=0: a process that never refits saves the table's 16 B of host memory per inner node (racc_hip_refit_create then refuses)
-    static const bool keep = [] { const char* e = std::getenv("RACC_REFIT_TOPOLOGY"); return !e || std::atoi(e) != 0; }();
-    if (!keep) return RACC_HIP_OK;
-    try {
-        auto topo = std::make_shared<RefitTopology>();
-        topo->nodeCount = node_count;
-        topo->words.resize(size_t(node_count) * 4);
-        for (uint32_t i = 0; i < node_count; ++i) std::memcpy(&topo->words[size_t(i) * 4], static_cast<const char*>(nodes64) + size_t(i) * 64, 16);
-        std::lock_guard<std::mutex> g(g_refitTopologyMutex);
-        g_refitTopology.emplace_back(*out, std::move(topo));
-    } catch (const std::bad_alloc&) {
-        // the upload itself succeeded and stays valid: the scene traces, it only cannot be refitted (racc_hip_refit_create says so)
-    }
-    return RACC_HIP_OK;
-}
-
-int racc_hip_scene_free(racc_hip_ctx* ctx, racc_hip_scene* scene) {
-    if (scene) {
-        std::lock_guard<std::mutex> g(g_refitTopologyMutex);
-        for (size_t i = 0; i < g_refitTopology.size(); ++i)
-            if (g_refitTopology[i].first == scene) { g_refitTopology[i] = g_refitTopology.back(); g_refitTopology.pop_back(); break; }
-    }
-    return raccSceneFreeBase(ctx, scene);
-}
-
 int racc_hip_refit_destroy(racc_hip_ctx* ctx, racc_hip_refit* r) {
     if (!ctx) return fail(RACC_HIP_ERR_INVALID, "refit_destroy: ctx is NULL");
     if (!r) return RACC_HIP_OK;
@@ -181,7 +139,7 @@ int racc_hip_refit_create(racc_hip_ctx* ctx, racc_hip_scene* scene, const uint32
     if (scene->nodesWide || scene->nodesWideQ || scene->nodesSoa)
         return fail(RACC_HIP_ERR_INVALID, "refit_create: the scene carries a 4-wide, compressed or SoA copy of the tree (kernel_variant 45 / 50, wide_below, the SoA variant); "
                                           "refit of those formats is not implemented and a stale copy would give wrong hits");
-    std::shared_ptr<const RefitTopology> topo = refitTopologyOf(scene);
+    std::shared_ptr<const RefitTopology> topo = sceneTopology(scene);
     if (!topo) return fail(RACC_HIP_ERR_INVALID, "refit_create: the blob's topology words were not kept for this scene (a device group's replica, RACC_REFIT_TOPOLOGY=0, or no host memory at upload)");
     if (index_count % 3 != 0) return fail(RACC_HIP_ERR_INVALID, "refit_create: index_count is not a multiple of 3");
     const uint32_t triCount = index_count / 3, nodeCount = topo->nodeCount, deviceNodes = scene->deviceNodes;

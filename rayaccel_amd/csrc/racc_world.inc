@@ -1,7 +1,8 @@
 // racc_world.inc — instancing: two-level scenes with per-instance transforms.  worldIntersectKernel and the C-ABI entries around it
-// (racc_hip_world_*).  Textually included by racc_hip_unit.hip BEHIND racc_hip.hip, racc_occlusion.inc and racc_refit.inc, so it sees the
-// context, the scenes' device pointers, fail() / HIP_TRY / checkWatchdog and the helpers of racc_device.inc, and changes none of them.
-// The reference has no instancing (one flattened scene, Scene.cpp:216-349); Embree's RTC_GEOMETRY_TYPE_INSTANCE is the usual counterpart.
+// (racc_hip_world_*).  Textually included by racc_hip_unit.hip BEHIND racc_hip.hip, racc_scene_registry.inc and racc_query.inc, so it sees
+// the context, the scenes' device pointers and owners, fail() / HIP_TRY / checkWatchdog, the helpers of racc_device.inc and the query
+// scaffold, and changes none of them.  The reference has no instancing (one flattened scene, Scene.cpp:216-349); Embree's
+// RTC_GEOMETRY_TYPE_INSTANCE is the usual counterpart.
 //
 // Contract (include/racc_hip.h): a world is an ordered list of (3x4 object-to-world transform, uploaded scene).  With inv the float-rounded
 // double-precision inverse (world_build.cpp), instance i sees the ray o' = inv (o, 1), d' = inv (d, 0) — each component the plain float
@@ -16,24 +17,21 @@
 // instance, plus rayPad (|ox| + |oy| + |oz|) added here on every side of every box, and the interval's end widened by 2^-20 of itself —
 // an instance that could still report t <= best is always entered, so no record can change.
 //
-// Structure (plain HIP, modelled on occludedKernel): a persistent grid of wave64 waves; rays handed out in chunks (the first chunk of
-// every wave statically, the rest from one cursor word); finished lanes found by ballot, ranked and refilled.  A lane is either at the top
-// level (`inst` = none; `node` = a top-level reference) or inside an instance (`inst` = its index; `node` = a reference into that scene's
-// BVH2 records).  Each scheduling iteration the wave votes for ONE of three steps: a pair step (every lane at a bottom-level leaf tests one
-// pair), a bottom-level inner step, or a top-level step (inner node: box tests; leaf: transform the ray and enter the instance).  Two
-// per-lane stacks, [level][thread] columns in LDS with deeper levels in a global spill: the top-level one survives an instance's traversal,
-// the bottom-level one is empty at every entry.  The launch's scratch (cursor word + both spills) is allocated, zeroed and freed in stream
-// order around the kernel: launches on different streams overlap each other and chained closest-hit batches.
+// Structure (plain HIP): the wavefront scaffold of racc_query.inc — the same ray feed, lane stack, BVH2 inner step and stream-ordered
+// scratch as occludedKernel.  A lane is either at the top level (`inst` = none; `node` = a top-level reference) or inside an instance
+// (`inst` = its index; `node` = a reference into that scene's BVH2 records).  Each scheduling iteration the wave votes for ONE of three
+// steps: a pair step (every lane at a bottom-level leaf tests one pair), a bottom-level inner step, or a top-level step (inner node: box
+// tests; leaf: transform the ray and enter the instance).  Two lane stacks: the top-level one survives an instance's traversal, the
+// bottom-level one is empty at every entry.
 
 namespace {
 
 constexpr int kWorldBlock = 256;
 constexpr int kWorldTopLds = 8;               // top-level stack levels in LDS (8 KB per workgroup)
 constexpr int kWorldBotLds = 12;              // bottom-level stack levels in LDS (12 KB per workgroup), as occludedKernel
-constexpr uint32_t kWorldWavesPerSimd = 5;    // grid: this many workgroups of four waves per CU (`make resources`: 86 VGPRs, 20 KB of LDS per workgroup: five fit)
+constexpr uint32_t kWorldWavesPerSimd = 5;    // grid: this many workgroups of four waves per CU (`make resources`: 84 VGPRs, 20 KB of LDS per workgroup: five fit)
 constexpr uint32_t kWorldRefillMin = 16;      // idle lanes that trigger a refill
 constexpr uint32_t kWorldLeafMin = 10;        // bottom-level leaf lanes that trigger a pair step
-constexpr uint32_t kWorldScratchHead = 64;    // words in front of the spill areas: word 0 = the ray cursor
 constexpr uint32_t kWorldNoInst = 0xFFFFFFFFu;
 
 struct WorldInstDev {          // one per instance, 32 B: where its scene lives
@@ -48,19 +46,16 @@ struct WorldArgs {
     const float4* rays;
     float4* results;
     uint32_t* instances;
-    uint32_t count;
+    QueryFeedArgs feed;
     const float4* topNodes;    // top-level tree as 64 B device records: words 0-1 child references, then Lx Ly Lz Rx Ry Rz as (min, max)
     const uint32_t* order;     // a top-level leaf (first | cnt << 24) names the instances order[first .. first + cnt)
     const float4* inv;         // three rows per instance
     const WorldInstDev* table;
     float rayPad;
-    uint32_t* cursor;          // one zeroed word per launch
-    uint32_t dynBase;          // rays handed out statically (grid waves x chunk): the cursor counts from here
-    uint32_t chunk;            // rays per dequeue, a multiple of 64
     uint32_t* spillTop;        // [topSpillLevels][gridThreads]
     uint32_t* spillBot;        // [botSpillLevels][gridThreads]
     uint32_t topSpillLevels, botSpillLevels, spillStride;
-    uint32_t refillMin, leafMin;
+    uint32_t leafMin;
     uint32_t maxIters;
     uint32_t* trips;
 };
@@ -80,7 +75,7 @@ __device__ __forceinline__ float4 worldHitRecord(const uint32_t* remap, int hitI
 __device__ __forceinline__ bool worldEmptyRef(uint32_t ref) { return ref < kLeafBase; }      // a leaf reference of count 0 (one-instance worlds)
 
 __global__ void __launch_bounds__(kWorldBlock) worldIntersectKernel(const WorldArgs a) {
-    __shared__ uint32_t topLds[kWorldTopLds * kWorldBlock];      // [level][thread]: conflict-free columns
+    __shared__ uint32_t topLds[kWorldTopLds * kWorldBlock];
     __shared__ uint32_t botLds[kWorldBotLds * kWorldBlock];
 
     const uint32_t tid = threadIdx.x;
@@ -88,11 +83,10 @@ __global__ void __launch_bounds__(kWorldBlock) worldIntersectKernel(const WorldA
     const uint32_t lane = tid & 63u;
     const uint32_t gwave = uint32_t(__builtin_amdgcn_readfirstlane(int(gtid >> 6)));
 
-    // the wave's current chunk [wBeg, wEnd): the first one is assigned statically (no start-up stampede on the cursor word)
-    uint32_t wBeg = gwave * a.chunk, wEnd;
-    if (wBeg >= a.count) { wBeg = 0u; wEnd = 0u; }
-    else wEnd = wBeg + min(a.chunk, a.count - wBeg);
-    bool exhausted = a.dynBase >= a.count;
+    RayFeed feed;
+    feed.start(a.feed, gwave);
+    LaneStack<kWorldTopLds, kWorldBlock> top{topLds + tid, a.spillTop, a.topSpillLevels, a.spillStride, gtid, 0u};
+    LaneStack<kWorldBotLds, kWorldBlock> bot{botLds + tid, a.spillBot, a.botSpillLevels, a.spillStride, gtid, 0u};
 
     // the world ray: origin, direction as given (what the instances transform), 1/d of the clamped direction for the top-level boxes
     float wox = 0.0f, woy = 0.0f, woz = 0.0f, wdx = 0.0f, wdy = 0.0f, wdz = 0.0f, wix = 0.0f, wiy = 0.0f, wiz = 0.0f;
@@ -102,100 +96,57 @@ __global__ void __launch_bounds__(kWorldBlock) worldIntersectKernel(const WorldA
     int bestIndex = -1;
     uint32_t bestInst = kWorldNoInst;
     // inside an instance: the object-space ray, {1/d, -o/d}, the shrinking limit, the hit, the scene
-    LaneRay r;
-    r.ox = r.oy = r.oz = r.dx = r.dy = r.dz = r.ix = r.iy = r.iz = r.ex = r.ey = r.ez = r.tNear = r.tFar = r.hitU = r.hitV = 0.0f;
-    r.hitIndex = -1;
+    LaneRay r = {};
     const float4* scNodes = nullptr;
     const float4* scPairs = nullptr;
-    uint32_t rayIdx = 0u, node = kEmpty, inst = kWorldNoInst, tsp = 0u, bsp = 0u;
+    uint32_t rayIdx = 0u, node = kEmpty, inst = kWorldNoInst;
 
     // next top-level reference from the stack; a ray that runs out of stack is finished: its record is written and its lane freed
     auto topPop = [&]() {
-        if (tsp == 0u) {
+        if (!top.pop(node)) {
             float4 out = make_float4(__uint_as_float(kInvalidTriangle), 0.0f, 0.0f, 0.0f);
             if (bestInst != kWorldNoInst) out = worldHitRecord(a.table[bestInst].remap, bestIndex, bestT, bestU, bestV);
             a.results[rayIdx] = out;
             a.instances[rayIdx] = bestInst;
             node = kEmpty;
-        } else {
-            --tsp;
-            node = tsp < uint32_t(kWorldTopLds) ? topLds[tsp * uint32_t(kWorldBlock) + tid]
-                                                : a.spillTop[size_t(tsp - uint32_t(kWorldTopLds)) * a.spillStride + gtid];
         }
-    };
-    auto topPush = [&](uint32_t ref) {
-        if (tsp < uint32_t(kWorldTopLds)) { topLds[tsp * uint32_t(kWorldBlock) + tid] = ref; ++tsp; }
-        else if (tsp - uint32_t(kWorldTopLds) < a.topSpillLevels) { a.spillTop[size_t(tsp - uint32_t(kWorldTopLds)) * a.spillStride + gtid] = ref; ++tsp; }
-        // (a validated tree cannot push deeper than its height + 1: the spill area is sized from it)
     };
     // next bottom-level reference; an instance whose stack is empty is finished: its result is composed (smallest t, ties to the lowest
     // instance index) and the lane goes back to the top level
     auto botPop = [&]() {
-        if (bsp == 0u) {
+        if (!bot.pop(node)) {
             if (r.hitIndex >= 0 && (bestInst == kWorldNoInst || r.tFar < bestT || (r.tFar == bestT && inst < bestInst))) {
                 bestT = r.tFar; bestU = r.hitU; bestV = r.hitV; bestIndex = r.hitIndex; bestInst = inst;
                 tCull = bestT;
             }
             inst = kWorldNoInst;
             topPop();
-        } else {
-            --bsp;
-            node = bsp < uint32_t(kWorldBotLds) ? botLds[bsp * uint32_t(kWorldBlock) + tid]
-                                                : a.spillBot[size_t(bsp - uint32_t(kWorldBotLds)) * a.spillStride + gtid];
         }
     };
 
     for (uint32_t iter = 0;; ++iter) {
-        if (iter >= a.maxIters) {      // watchdog, like the closest-hit kernels: the wave gives up, the host hears about it at the next synchronisation
-            if (lane == 0u) __hip_atomic_fetch_add(a.trips, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            break;
-        }
+        if (watchdogTripped(iter, a.maxIters, a.trips, lane)) break;
 
         // ================= refill: idle lanes take the next rays of the wave's chunk =================
-        const uint64_t emptyMask = __ballot(node == kEmpty);
-        const uint32_t nEmpty = uint32_t(__popcll(emptyMask));
-        if (nEmpty == 64u || (nEmpty >= a.refillMin && !(exhausted && wBeg == wEnd))) {
-            if (wBeg == wEnd && !exhausted) {
-                uint32_t b = 0u;
-                if (lane == 0u) b = __hip_atomic_fetch_add(a.cursor, a.chunk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                b = uint32_t(__builtin_amdgcn_readfirstlane(int(b)));
-                const uint64_t start = uint64_t(a.dynBase) + b;
-                if (start >= uint64_t(a.count)) exhausted = true;
-                else { wBeg = uint32_t(start); wEnd = wBeg + min(a.chunk, a.count - wBeg); }
-            }
-            if (wBeg == wEnd) {
-                if (nEmpty == 64u) break;      // no ray left to draw and none in flight
+        const bool more = feed.refill(a.feed, node == kEmpty, lane, [&](uint32_t idx) {
+            float4 q0, q1;
+            if (!admitRay(a.rays, idx, q0, q1)) {
+                a.results[idx] = make_float4(__uint_as_float(kInvalidTriangle), 0.0f, 0.0f, 0.0f);
+                a.instances[idx] = kWorldNoInst;
             } else {
-                const uint32_t take = min(nEmpty, wEnd - wBeg);
-                const uint32_t rank = laneRank(emptyMask);
-                if (node == kEmpty && rank < take) {
-                    const uint32_t idx = wBeg + rank;
-                    float4 q0, q1;
-                    loadRay(a.rays, idx, false, q0, q1);
-                    const bool valid = isfinite(q0.x) && isfinite(q0.y) && isfinite(q0.z) && isfinite(q0.w) &&
-                                       isfinite(q1.x) && isfinite(q1.y) && isfinite(q1.z) && !isnan(q1.w);
-                    if (!valid) {      // rays the oracle rejects (racc_oracle.c:183-191)
-                        a.results[idx] = make_float4(__uint_as_float(kInvalidTriangle), 0.0f, 0.0f, 0.0f);
-                        a.instances[idx] = kWorldNoInst;
-                    } else {
-                        const float eps = 1e-10f;      // the clamp of Kernels.h:149-157, here only for the top-level box tests
-                        wox = q0.x; woy = q0.y; woz = q0.z; tNear = q0.w;
-                        wdx = q1.x; wdy = q1.y; wdz = q1.z; tMax = q1.w;
-                        wix = 1.0f / ((fabsf(wdx) < eps) ? copysignf(eps, wdx) : wdx);
-                        wiy = 1.0f / ((fabsf(wdy) < eps) ? copysignf(eps, wdy) : wdy);
-                        wiz = 1.0f / ((fabsf(wdz) < eps) ? copysignf(eps, wdz) : wdz);
-                        pad = a.rayPad * (fabsf(wox) + fabsf(woy) + fabsf(woz));
-                        bestInst = kWorldNoInst; bestIndex = -1; bestT = bestU = bestV = 0.0f;
-                        tCull = tMax;
-                        rayIdx = idx;
-                        inst = kWorldNoInst;
-                        node = 0x80000000u;      // the top-level root
-                        tsp = 0u; bsp = 0u;
-                    }
-                }
-                wBeg += take;
+                wox = q0.x; woy = q0.y; woz = q0.z; tNear = q0.w;
+                wdx = q1.x; wdy = q1.y; wdz = q1.z; tMax = q1.w;
+                wix = 1.0f / clampDir(wdx); wiy = 1.0f / clampDir(wdy); wiz = 1.0f / clampDir(wdz);      // the clamp here only for the top-level box tests
+                pad = a.rayPad * (fabsf(wox) + fabsf(woy) + fabsf(woz));
+                bestInst = kWorldNoInst; bestIndex = -1; bestT = bestU = bestV = 0.0f;
+                tCull = tMax;
+                rayIdx = idx;
+                inst = kWorldNoInst;
+                node = 0x80000000u;      // the top-level root
+                top.height = 0u; bot.height = 0u;
             }
-        }
+        });
+        if (!more) break;
 
         // ================= vote: one pair step, one bottom-level inner step or one top-level step =================
         const bool inBot = inst != kWorldNoInst;
@@ -215,24 +166,7 @@ __global__ void __launch_bounds__(kWorldBlock) worldIntersectKernel(const WorldA
                 else botPop();
             }
         } else if (nBot != 0u && nBot >= nTop) {
-            if (isBotInner) {      // the node rule of the closest-hit kernels (racc_kernel_v8.inc's C++ iteration), tRay = the current tFar
-                const float4* np = scNodes + size_t(node & 0x7FFFFFFFu) * 4;
-                const uint2 k2 = *reinterpret_cast<const uint2*>(np);
-                const float4 d1 = np[1], d2 = np[2], d3 = np[3];
-                const float tRay = r.tFar;
-                float tFirst, tLast;
-                slabPair(d1, d2, d3, r.ix, r.iy, r.iz, r.ex, r.ey, r.ez, r.tNear, tRay, tFirst, tLast);
-                const float firstDiff = tRay - tFirst, lastDiff = tRay - tLast;
-                if (firstDiff + lastDiff != 0.0f) {                               // Kernels.h:192
-                    const bool lastNearer = tLast < tFirst;                       // signbit(tLast - tFirst), Kernels.h:193
-                    if ((tFirst != tRay) & (tLast != tRay)) {                     // fmax(tFirst, tLast) != tRay, Kernels.h:194: both entered
-                        const uint32_t farKid = lastNearer ? k2.x : k2.y;
-                        if (bsp < uint32_t(kWorldBotLds)) { botLds[bsp * uint32_t(kWorldBlock) + tid] = farKid; ++bsp; }
-                        else if (bsp - uint32_t(kWorldBotLds) < a.botSpillLevels) { a.spillBot[size_t(bsp - uint32_t(kWorldBotLds)) * a.spillStride + gtid] = farKid; ++bsp; }
-                    }
-                    node = lastNearer ? k2.y : k2.x;
-                } else botPop();
-            }
+            if (isBotInner && !bvh2InnerStep(scNodes, node, r, r.tFar, bot)) botPop();      // tRay = the current tFar
         } else if (nTop != 0u) {
             if (isTop) {
                 if (int(node) < 0) {      // top-level inner node: both child boxes, padded, against [tNear, widened best t]
@@ -249,7 +183,7 @@ __global__ void __launch_bounds__(kWorldBlock) worldIntersectKernel(const WorldA
                     const bool hitLast = tLast != tEnd && !worldEmptyRef(k2.y);
                     if (hitFirst && hitLast) {
                         const bool lastNearer = tLast < tFirst;
-                        topPush(lastNearer ? k2.x : k2.y);
+                        top.push(lastNearer ? k2.x : k2.y);
                         node = lastNearer ? k2.y : k2.x;
                     } else if (hitFirst) node = k2.x;
                     else if (hitLast) node = k2.y;
@@ -257,7 +191,7 @@ __global__ void __launch_bounds__(kWorldBlock) worldIntersectKernel(const WorldA
                 } else {                  // top-level leaf: enter its next instance (the rest of the range waits on the top-level stack)
                     const uint32_t first = node & 0xFFFFFFu, cnt = node >> 24;
                     const uint32_t id = a.order[first];
-                    if (cnt > 1u) topPush(((cnt - 1u) << 24) | (first + 1u));
+                    if (cnt > 1u) top.push(((cnt - 1u) << 24) | (first + 1u));
                     const float4 m0 = a.inv[size_t(id) * 3], m1 = a.inv[size_t(id) * 3 + 1], m2 = a.inv[size_t(id) * 3 + 2];
                     // o' = inv (o, 1), d' = inv (d, 0): ((m0 x + m1 y) + m2 z) + m3, left to right (-ffp-contract=off: nothing is fused)
                     const float ox = ((m0.x * wox + m0.y * woy) + m0.z * woz) + m0.w;
@@ -268,30 +202,18 @@ __global__ void __launch_bounds__(kWorldBlock) worldIntersectKernel(const WorldA
                     const float dz = (m2.x * wdx + m2.y * wdy) + m2.z * wdz;
                     if (!(isfinite(ox) && isfinite(oy) && isfinite(oz) && isfinite(dx) && isfinite(dy) && isfinite(dz))) topPop();      // the closest-hit path rejects this ray: h_i is a miss
                     else {
-                        const float eps = 1e-10f;   // Kernels.h:149-157
-                        r.ox = ox; r.oy = oy; r.oz = oz; r.tNear = tNear;
-                        r.dx = (fabsf(dx) < eps) ? copysignf(eps, dx) : dx;
-                        r.dy = (fabsf(dy) < eps) ? copysignf(eps, dy) : dy;
-                        r.dz = (fabsf(dz) < eps) ? copysignf(eps, dz) : dz;
-                        r.tFar = tMax;              // the ray's own maxT, whatever the other instances have reported
-                        r.ix = 1.0f / r.dx; r.iy = 1.0f / r.dy; r.iz = 1.0f / r.dz;      // Kernels.h:159-160
-                        r.ex = -r.ox * r.ix; r.ey = -r.oy * r.iy; r.ez = -r.oz * r.iz;
-                        r.hitIndex = -1; r.hitU = 0.0f; r.hitV = 0.0f;
+                        setLaneRay(r, ox, oy, oz, dx, dy, dz, tNear, tMax);      // the ray's own maxT, whatever the other instances have reported
                         const WorldInstDev e = a.table[id];
                         scNodes = e.nodes; scPairs = e.pairs;
                         inst = id;
                         node = 0x80000000u;     // Kernels.h:164
-                        bsp = 0u;
+                        bot.height = 0u;
                     }
                 }
             }
         }
     }
 }
-
-// scene -> owning context, for every scene uploaded through racc_hip_scene_upload (racc_hip_world_create refuses a foreign scene)
-std::mutex g_worldOwnerMutex;
-std::vector<std::pair<const racc_hip_scene*, const racc_hip_ctx*>> g_worldOwner;
 
 }  // namespace
 
@@ -359,76 +281,37 @@ int worldCommit(racc_hip_world* w, const float* transforms12) try {
     return fail(RACC_HIP_ERR_NOMEM, "world: out of host memory");
 }
 
-// Enqueues one world launch on `st`: scratch (cursor word + both spills) allocated, zeroed and freed in stream order around the kernel.
+// Enqueues one world launch on `st` (scratch: racc_query.inc; here the cursor word and both spills).
 int launchWorld(racc_hip_ctx* ctx, const racc_hip_world* w, const void* dRays, void* dResults, uint32_t* dInstances, uint32_t count, hipStream_t st) {
-    if (count > 0xFF000000u) return fail(RACC_HIP_ERR_LIMIT, "world_intersect: more than 0xFF000000 rays in one launch");      // (the cursor word counts past `count` by at most grid waves x chunk)
-    // RACC_WORLD_WAVES / RACC_WORLD_REFILL / RACC_WORLD_LEAF: A/B of the grid size and the two vote thresholds (tools/bench_world.py), results do not depend on them
-    static const uint32_t envWaves = [] { const char* e = std::getenv("RACC_WORLD_WAVES"); return e && std::atoi(e) > 0 && std::atoi(e) <= 8 ? uint32_t(std::atoi(e)) : kWorldWavesPerSimd; }();
-    static const uint32_t envRefill = [] { const char* e = std::getenv("RACC_WORLD_REFILL"); return e && std::atoi(e) > 0 && std::atoi(e) <= 64 ? uint32_t(std::atoi(e)) : kWorldRefillMin; }();
-    static const uint32_t envLeaf = [] { const char* e = std::getenv("RACC_WORLD_LEAF"); return e && std::atoi(e) > 0 && std::atoi(e) <= 64 ? uint32_t(std::atoi(e)) : kWorldLeafMin; }();
-    uint32_t blocks = uint32_t(ctx->numCUs) * envWaves;
-    const uint32_t blocksNeeded = (count + uint32_t(kWorldBlock) - 1u) / uint32_t(kWorldBlock);
-    if (blocks > blocksNeeded) blocks = blocksNeeded;
-    const uint32_t gridThreads = blocks * uint32_t(kWorldBlock);
-
+    // RACC_WORLD_WAVES / RACC_WORLD_REFILL / RACC_WORLD_LEAF: A/B of the grid size and the two vote thresholds (tools/bench_world.py)
+    static const uint32_t envWaves = queryTunable("RACC_WORLD_WAVES", 1, 8, kWorldWavesPerSimd);
+    static const uint32_t envRefill = queryTunable("RACC_WORLD_REFILL", 1, 64, kWorldRefillMin);
+    static const uint32_t envLeaf = queryTunable("RACC_WORLD_LEAF", 1, 64, kWorldLeafMin);
+    QueryGrid g;
     WorldArgs a;
+    if (int rc = queryGrid(ctx, count, uint32_t(kWorldBlock), envWaves, "world_intersect: more than 0xFF000000 rays in one launch", g, a.feed)) return rc;
     a.rays = static_cast<const float4*>(dRays);
     a.results = static_cast<float4*>(dResults);
     a.instances = dInstances;
-    a.count = count;
     a.topNodes = w->topNodes; a.order = w->order; a.inv = w->inv; a.table = w->table;
     a.rayPad = w->rayPad;
-    a.chunk = count >= (1u << 19) ? 128u : 64u;
-    a.dynBase = (gridThreads / 64u) * a.chunk;
     a.topSpillLevels = w->info.spill_levels;
     a.botSpillLevels = w->info.bottom_spill_levels;
-    a.spillStride = gridThreads;
-    a.refillMin = envRefill; a.leafMin = envLeaf;
+    a.spillStride = g.gridThreads;
+    a.feed.refillMin = envRefill; a.leafMin = envLeaf;
     a.maxIters = ctx->maxIters;
     a.trips = ctx->devTrips;
-
-    uint32_t* scratch = nullptr;
-    const size_t bytes = (size_t(kWorldScratchHead) + size_t(a.topSpillLevels + a.botSpillLevels) * gridThreads) * sizeof(uint32_t);
-    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&scratch), bytes, st), "hipMallocAsync(world scratch)");
-    hipError_t e = hipMemsetAsync(scratch, 0, size_t(kWorldScratchHead) * sizeof(uint32_t), st);
-    if (e == hipSuccess) {
-        a.cursor = scratch;
-        a.spillTop = scratch + kWorldScratchHead;
-        a.spillBot = a.spillTop + size_t(a.topSpillLevels) * gridThreads;
-        hipLaunchKernelGGL(worldIntersectKernel, dim3(blocks), dim3(kWorldBlock), 0, st, a);
-        e = hipGetLastError();
-    }
-    const hipError_t e2 = hipFreeAsync(scratch, st);
-    if (e != hipSuccess) return fail(RACC_HIP_ERR_DEVICE, "launch worldIntersectKernel", e);
-    if (e2 != hipSuccess) return fail(RACC_HIP_ERR_DEVICE, "hipFreeAsync(world scratch)", e2);
-    return RACC_HIP_OK;
+    return withQueryScratch(size_t(a.topSpillLevels + a.botSpillLevels) * g.gridThreads, st, "launch worldIntersectKernel", [&](uint32_t* scratch) {
+        a.feed.cursor = scratch;
+        a.spillTop = scratch + kQueryScratchHead;
+        a.spillBot = a.spillTop + size_t(a.topSpillLevels) * g.gridThreads;
+        hipLaunchKernelGGL(worldIntersectKernel, dim3(g.blocks), dim3(kWorldBlock), 0, st, a);
+    });
 }
 
 }  // namespace
 
 extern "C" {
-
-// racc_refit.inc's upload / free are compiled under other names too (racc_hip_unit.hip): the public entries note who owns a scene.
-int racc_hip_scene_upload(racc_hip_ctx* ctx, const void* nodes64, uint32_t node_count, const void* pairs48, uint32_t pair_count,
-                          const uint32_t* remap, uint32_t remap_count, racc_hip_scene** out) {
-    if (int rc = raccSceneUploadRefit(ctx, nodes64, node_count, pairs48, pair_count, remap, remap_count, out)) return rc;
-    try {
-        std::lock_guard<std::mutex> g(g_worldOwnerMutex);
-        g_worldOwner.emplace_back(*out, ctx);
-    } catch (const std::bad_alloc&) {
-        // the upload itself succeeded and stays valid: the scene traces, it only cannot become an instance (racc_hip_world_create says so)
-    }
-    return RACC_HIP_OK;
-}
-
-int racc_hip_scene_free(racc_hip_ctx* ctx, racc_hip_scene* scene) {
-    if (scene) {
-        std::lock_guard<std::mutex> g(g_worldOwnerMutex);
-        for (size_t i = 0; i < g_worldOwner.size(); ++i)
-            if (g_worldOwner[i].first == scene) { g_worldOwner[i] = g_worldOwner.back(); g_worldOwner.pop_back(); break; }
-    }
-    return raccSceneFreeRefit(ctx, scene);
-}
 
 int racc_hip_world_destroy(racc_hip_ctx* ctx, racc_hip_world* w) {
     if (!ctx) return fail(RACC_HIP_ERR_INVALID, "world_destroy: ctx is NULL");
@@ -450,20 +333,15 @@ int racc_hip_world_create(racc_hip_ctx* ctx, const float* transforms12, const ra
     if (!count) return fail(RACC_HIP_ERR_INVALID, "world_create: count is 0: a world has at least one instance");
     if (count > RACC_HIP_WORLD_MAX_INSTANCES) return fail(RACC_HIP_ERR_INVALID, "world_create: more than 2^20 instances");
     uint32_t maxHeight = 0;
-    {
-        std::lock_guard<std::mutex> g(g_worldOwnerMutex);
-        const racc_hip_scene* known = nullptr;      // (runs of one scene are the common case)
-        for (uint32_t i = 0; i < count; ++i) {
-            const racc_hip_scene* s = scenes[i];
-            if (!s) return fail(RACC_HIP_ERR_INVALID, "world_create: a scene is NULL");
-            if (s != known) {
-                bool own = false;
-                for (const auto& e : g_worldOwner) if (e.first == s) { own = e.second == ctx; break; }
-                if (!own) return fail(RACC_HIP_ERR_INVALID, "world_create: a scene was not uploaded through racc_hip_scene_upload on this context (another context's scene, or a device group's replica)");
-                known = s;
-            }
-            if (s->info.inner_height > maxHeight) maxHeight = s->info.inner_height;
+    const racc_hip_scene* known = nullptr;      // (runs of one scene are the common case: one registry lookup per run)
+    for (uint32_t i = 0; i < count; ++i) {
+        const racc_hip_scene* s = scenes[i];
+        if (!s) return fail(RACC_HIP_ERR_INVALID, "world_create: a scene is NULL");
+        if (s != known) {
+            if (sceneOwner(s) != ctx) return fail(RACC_HIP_ERR_INVALID, "world_create: a scene was not uploaded through racc_hip_scene_upload on this context (another context's scene, or a device group's replica)");
+            known = s;
         }
+        if (s->info.inner_height > maxHeight) maxHeight = s->info.inner_height;
     }
     HIP_TRY(hipSetDevice(ctx->device), "hipSetDevice");
     racc_hip_world* w = new (std::nothrow) racc_hip_world();
@@ -524,28 +402,9 @@ int racc_hip_world_intersect(racc_hip_ctx* ctx, const racc_hip_world* w, const v
     if (!count) return RACC_HIP_OK;
     if (!rays || !results || !instances) return fail(RACC_HIP_ERR_INVALID, "world_intersect: rays/results/instances is NULL");
     HIP_TRY(hipSetDevice(ctx->device), "hipSetDevice");
-    // everything of the call is its own (stream, staging arrays): several threads may be in here at once
-    hipStream_t st = nullptr;
-    void* dRays = nullptr;
-    void* dOut = nullptr;
-    void* dInst = nullptr;
-    int rc = RACC_HIP_OK;
-    hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc(&dRays, size_t(count) * 32);
-    if (e == hipSuccess) e = hipMalloc(&dOut, size_t(count) * 16);
-    if (e == hipSuccess) e = hipMalloc(&dInst, size_t(count) * 4);
-    if (e == hipSuccess) e = hipMemcpyAsync(dRays, rays, size_t(count) * 32, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) rc = launchWorld(ctx, w, dRays, dOut, static_cast<uint32_t*>(dInst), count, st);
-    if (e == hipSuccess && rc == RACC_HIP_OK) e = hipMemcpyAsync(results, dOut, size_t(count) * 16, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && rc == RACC_HIP_OK) e = hipMemcpyAsync(instances, dInst, size_t(count) * 4, hipMemcpyDeviceToHost, st);
-    if (st) { const hipError_t es = hipStreamSynchronize(st); if (e == hipSuccess) e = es; }
-    if (dRays) hipFree(dRays);
-    if (dOut) hipFree(dOut);
-    if (dInst) hipFree(dInst);
-    if (st) hipStreamDestroy(st);
-    if (rc != RACC_HIP_OK) return rc;
-    if (e != hipSuccess) return fail(RACC_HIP_ERR_DEVICE, "world_intersect (host arrays)", e);
-    return checkWatchdog(ctx);
+    return runStagedQuery(ctx, "world_intersect (host arrays)", rays, count, results, size_t(count) * 16, instances, size_t(count) * 4, [&](void* dRays, void* dOut, void* dInst, hipStream_t st) {
+        return launchWorld(ctx, w, dRays, dOut, static_cast<uint32_t*>(dInst), count, st);
+    });
 }
 
 }  // extern "C"

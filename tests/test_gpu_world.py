@@ -5,6 +5,9 @@ world_helpers.compose — the specification's ray transform in numpy.float32 wit
 the ray's own maxT, smallest t, then lowest instance index.  Every device output carries guard records behind `count`, which must come
 back untouched."""
 import ctypes as C
+import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -19,6 +22,7 @@ from world_helpers import IDENTITY, NO_INSTANCE, affine, assert_world_exact, com
 pytestmark = pytest.mark.gpu
 
 GUARD = 16
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def prepare(transforms, blobs_list):
@@ -342,6 +346,81 @@ def test_update_after_a_member_scene_was_refitted(wd, small_host):
     world.destroy()
     refit.destroy()
     scene.destroy()
+
+
+# ------------------------------------------------------------------------------------------------------------ the scene registry
+def test_registry_survives_frees_in_between(wd, small_host, small_default_host):
+    """Refit and instancing look a scene up in one registry (racc_scene_registry.inc): uploads, frees and both lookups interleaved on one
+    context, then the refitted scene C — traced plainly and as a world — against the host refit's blobs uploaded fresh."""
+    ctx, sc, rays = wd["ctx"], wd["sc"], wd["rays"][:4096]
+    a = ctx.upload_scene(small_host.nodes, small_host.pairs, small_host.remap)
+    b = ctx.upload_scene(small_default_host.nodes, small_default_host.pairs, small_default_host.remap)
+    c = ctx.upload_scene(small_host.nodes, small_host.pairs, small_host.remap)
+    b.destroy()
+    refit = ctx.create_refit(c, sc["indices"], len(sc["vertices"]))
+    transforms = overlapping_transforms(sc)[:2]
+    world = ctx.create_world([(transforms[0], a), (transforms[1], c)])
+    check_world(ctx, world, transforms, [small_host.blobs()] * 2, rays, "world of (A, C) after B was freed", host_too=False)
+    world.destroy()
+    a.destroy()
+    v = displaced(sc["vertices"], 3.0, phase=0.2)
+    refit.refit(v)
+    blobs = ra.host_refit(small_host.blobs(), v, sc["indices"])
+    fresh = ctx.upload_scene(blobs["nodes"], blobs["pairs"], blobs["remap"])
+    want = ctx.intersect(fresh, None, rays)
+    assert (want["t"].view(np.uint32) != ctx.intersect(wd["scene"], None, rays)["t"].view(np.uint32)).any(), "the refit must change the answer for the test to mean anything"
+    assert_bit_exact(ctx.intersect(c, None, rays), want, "C refitted after A and B were freed, against the host refit uploaded fresh")
+    world = ctx.create_world([(IDENTITY, c)])
+    got, got_inst = world.intersect(rays)
+    assert_bit_exact(got, want, "world of C, against the host refit uploaded fresh")
+    assert np.array_equal(got_inst, np.where(want["triangle"] != MISS, 0, NO_INSTANCE).astype(np.uint32))
+    world.destroy()      # the documented order: a world before its scenes, a refit handle before its scene
+    refit.destroy()
+    fresh.destroy()
+    c.destroy()
+
+
+_NO_TOPOLOGY_CHILD = r"""
+import sys
+import numpy as np
+sys.path.insert(0, sys.argv[1])
+import rayaccel_amd as ra
+d = np.load(sys.argv[2])
+with ra.Context(device=0) as ctx:
+    scene = ctx.upload_scene(d["nodes"], d["pairs"], d["remap"])
+    try:
+        ctx.create_refit(scene, d["indices"], int(d["vertex_count"])).destroy()
+        refusal = ""
+    except ra.RaccError as e:
+        refusal = str(e)
+    plain = ctx.intersect(scene, None, d["rays"])
+    world = ctx.create_world([(np.eye(3, 4, dtype=np.float32), scene)])
+    got, inst = world.intersect(d["rays"])
+    world.destroy()
+    scene.destroy()
+np.savez(sys.argv[3], refusal=refusal, plain=plain, world=got, inst=inst)
+"""
+
+
+def test_without_kept_topology_only_refit_is_refused(tmp_path, wd, small_host):
+    """RACC_REFIT_TOPOLOGY=0 is read once per process, hence a child: create_refit is refused, the scene still traces and still becomes an
+    instance (its owner is registered all the same), with this process's records."""
+    ctx, sc, rays = wd["ctx"], wd["sc"], wd["rays"][:4096]
+    inputs, outputs = str(tmp_path / "in.npz"), str(tmp_path / "out.npz")
+    np.savez(inputs, nodes=small_host.nodes, pairs=small_host.pairs, remap=small_host.remap, indices=sc["indices"], vertex_count=len(sc["vertices"]), rays=rays)
+    p = subprocess.run([sys.executable, "-c", _NO_TOPOLOGY_CHILD, ROOT, inputs, outputs], capture_output=True, text=True, timeout=120,
+                       env=dict(os.environ, RACC_REFIT_TOPOLOGY="0"))
+    assert p.returncode == 0, p.stderr[-2000:]
+    out = np.load(outputs)
+    assert "topology words" in str(out["refusal"]), "create_refit under RACC_REFIT_TOPOLOGY=0: %r" % str(out["refusal"])
+    want = ctx.intersect(wd["scene"], None, rays)
+    assert 0 < (want["triangle"] != MISS).sum() < len(rays)      # hits and misses
+    assert_bit_exact(out["plain"].view(synth.RESULT_DTYPE), want, "intersect under RACC_REFIT_TOPOLOGY=0")
+    world = ctx.create_world([(IDENTITY, wd["scene"])])
+    got, got_inst = world.intersect(rays)
+    world.destroy()
+    assert_bit_exact(out["world"].view(synth.RESULT_DTYPE), got, "world of one instance under RACC_REFIT_TOPOLOGY=0")
+    assert np.array_equal(out["inst"], got_inst)
 
 
 @pytest.mark.parametrize("world_first", [False, True])
