@@ -337,7 +337,26 @@ int racc_hip_refit_download(racc_hip_ctx*, racc_hip_refit*, void* nodes64_out, u
  * (hipStream_t as void*, NULL = the default stream); complete after racc_hip_stream_synchronize, which also reports a watchdog trip.
  * ctx is checked first, then world; count == 0 is a successful no-op.
  * racc_hip_world_intersect: host arrays, blocking, callable from several threads at once (every call brings its own stream and staging).
- * Out of scope: an instanced occlusion query, environment sampling on a miss, racc::render carrying instance ids (its Result has no room),
+ *
+ * Occlusion (any-hit) on a world — the shadow / visibility ray of a caller who uses instancing, as racc_hip_occluded* is for a scene.
+ * occluded[i] = 1 iff some instance's closest-hit result h_i, as defined above, is a hit; equivalently, iff racc_hip_world_intersect*
+ * reports instance != 0xFFFFFFFF for rays[i].  That holds for every ray: there is no exception class.  Inside an instance the rule is that
+ * of racc_hip_occluded*: the transformed ray with the ray's own minT / maxT, the limit never shrunk, the pair test up to its
+ * accept / reject decision, stop at the first accepted pair.  Rays the closest-hit path rejects give 0 — in world space, or after every
+ * transform; a rejected transformed ray only skips that instance.  The order in which instances are visited is free; the top level is
+ * walked with the ray's own maxT (widened as the closest-hit kernel widens its limit), which is never less than the closest-hit kernel's
+ * limit, so every instance that could report a hit is entered unless the ray is already decided.  One byte per ray: no Result, no instance
+ * index, no remap gather.  Its own kernel (worldOccludedKernel, rayaccel_amd/csrc/racc_world_occlusion.inc), a launch owning its scratch
+ * memory like the closest-hit world launch.
+ * racc_hip_world_occluded_device: device-resident Ray[count] in, uint8[count] out, asynchronous on `stream`; complete after
+ * racc_hip_stream_synchronize, which also reports a watchdog trip.  ctx is checked first, then world, then that the world is this
+ * context's; count == 0 is a successful no-op; NULL arrays are refused.  The ordering contract with racc_hip_world_update is that of
+ * racc_hip_world_intersect_device (the update synchronises the context first).
+ * racc_hip_world_occluded: host arrays, blocking, callable from several threads at once (every call brings its own stream and staging).
+ * Out of scope for the occlusion query: reporting which instance occluded, instance or ray masks, device groups, the 4-wide formats,
+ * multi-level instancing, wiring into the path tracers or racc::render.
+ *
+ * Out of scope: environment sampling on a miss, racc::render carrying instance ids (its Result has no room),
  * device groups, the 4-wide kernels, multi-level instancing (an instance of a world). */
 #define RACC_HIP_WORLD_MAX_INSTANCES (1u << 20)
 typedef struct racc_hip_world racc_hip_world;
@@ -356,6 +375,8 @@ int racc_hip_world_destroy(racc_hip_ctx*, racc_hip_world*);
 int racc_hip_world_get_info(const racc_hip_world*, racc_hip_world_info* info);
 int racc_hip_world_intersect_device(racc_hip_ctx*, const racc_hip_world*, const void* d_rays, void* d_results, uint32_t* d_instances, uint32_t count, void* stream);
 int racc_hip_world_intersect(racc_hip_ctx*, const racc_hip_world*, const void* rays, void* results, uint32_t* instances, uint32_t count);
+int racc_hip_world_occluded_device(racc_hip_ctx*, const racc_hip_world*, const void* d_rays, uint8_t* d_occluded, uint32_t count, void* stream);
+int racc_hip_world_occluded(racc_hip_ctx*, const racc_hip_world*, const void* rays, uint8_t* occluded, uint32_t count);
 
 int racc_hip_get_launch_info(racc_hip_ctx* ctx, uint32_t lane, racc_hip_launch_info* info);
 /* With racc_hip_options::time_kernels: durations (ms, HIP events on the stream each launch went to) of the lane's traversal

@@ -12,3 +12,4 @@
 #include "racc_refit.inc"
 #include <array>
 #include "racc_world.inc"
+#include "racc_world_occlusion.inc"

@@ -1,5 +1,6 @@
 // racc_world.inc — instancing: two-level scenes with per-instance transforms.  worldIntersectKernel and the C-ABI entries around it
-// (racc_hip_world_*).  Textually included by racc_hip_unit.hip BEHIND racc_hip.hip, racc_scene_registry.inc and racc_query.inc, so it sees
+// (racc_hip_world_*); the any-hit query on worlds, worldOccludedKernel, is racc_world_occlusion.inc behind this file, on the helpers
+// here.  Textually included by racc_hip_unit.hip BEHIND racc_hip.hip, racc_scene_registry.inc and racc_query.inc, so it sees
 // the context, the scenes' device pointers and owners, fail() / HIP_TRY / checkWatchdog, the helpers of racc_device.inc and the query
 // scaffold, and changes none of them.  The reference has no instancing (one flattened scene, Scene.cpp:216-349); Embree's
 // RTC_GEOMETRY_TYPE_INSTANCE is the usual counterpart.
@@ -74,6 +75,75 @@ __device__ __forceinline__ float4 worldHitRecord(const uint32_t* remap, int hitI
 
 __device__ __forceinline__ bool worldEmptyRef(uint32_t ref) { return ref < kLeafBase; }      // a leaf reference of count 0 (one-instance worlds)
 
+// ---- what the world kernels share (worldIntersectKernel here, worldOccludedKernel in racc_world_occlusion.inc): the world ray, the
+// top-level step and the transform-and-enter rule.  One statement of each; the kernels differ in what they keep per lane, in the interval
+// end they hand to the top level and in what an empty stack means.
+
+// The world ray of a lane: origin and direction as given (what the instances transform), 1/d of the clamped direction for the top-level
+// boxes (the clamp here only for those box tests), the ray's own interval, and the pad this ray adds to every top-level box.
+struct WorldRay {
+    float ox, oy, oz, dx, dy, dz, ix, iy, iz;
+    float tNear, tMax, pad;
+};
+
+__device__ __forceinline__ void setWorldRay(WorldRay& w, const float4 q0, const float4 q1, float rayPad) {
+    w.ox = q0.x; w.oy = q0.y; w.oz = q0.z; w.tNear = q0.w;
+    w.dx = q1.x; w.dy = q1.y; w.dz = q1.z; w.tMax = q1.w;
+    w.ix = 1.0f / clampDir(w.dx); w.iy = 1.0f / clampDir(w.dy); w.iz = 1.0f / clampDir(w.dz);
+    w.pad = rayPad * (fabsf(w.ox) + fabsf(w.oy) + fabsf(w.oz));
+}
+
+// The interval end the top level is walked with for a limit t: 2^-20 of itself past it — past every t <= the limit an instance could
+// still report (world_build.cpp has the bound).
+__device__ __forceinline__ float worldWidenedEnd(float t) { return t + fmaxf(fabsf(t) * 9.5367431640625e-07f, 1e-30f); }
+
+// Top-level inner node: both child boxes, padded, against [tNear, tEnd] (tEnd = worldWidenedEnd of the kernel's limit).  `node` becomes
+// the next reference, the farther child goes on the stack if both were entered; if neither was, pop() — the kernel's rule for what comes
+// next, and for the empty stack.  (Continuations, not a returned flag: the closest-hit kernel compiles to what it was before the split.)
+template <class Stack, class Pop>
+__device__ __forceinline__ void worldTopInnerStep(const float4* topNodes, uint32_t& node, const WorldRay& w, float tEnd, Stack& top, Pop&& pop) {
+    const float4* np = topNodes + size_t(node & 0x7FFFFFFFu) * 4;
+    const uint2 k2 = *reinterpret_cast<const uint2*>(np);
+    float4 d1 = np[1], d2 = np[2], d3 = np[3];
+    d1.x -= w.pad; d1.y += w.pad; d1.z -= w.pad; d1.w += w.pad;
+    d2.x -= w.pad; d2.y += w.pad; d2.z -= w.pad; d2.w += w.pad;
+    d3.x -= w.pad; d3.y += w.pad; d3.z -= w.pad; d3.w += w.pad;
+    float tFirst, tLast;
+    slabPair(d1, d2, d3, w.ix, w.iy, w.iz, -w.ox * w.ix, -w.oy * w.iy, -w.oz * w.iz, w.tNear, tEnd, tFirst, tLast);
+    const bool hitFirst = tFirst != tEnd && !worldEmptyRef(k2.x);      // (slabPair: tEnd doubles as "missed")
+    const bool hitLast = tLast != tEnd && !worldEmptyRef(k2.y);
+    if (hitFirst && hitLast) {
+        const bool lastNearer = tLast < tFirst;
+        top.push(lastNearer ? k2.x : k2.y);
+        node = lastNearer ? k2.y : k2.x;
+    } else if (hitFirst) node = k2.x;
+    else if (hitLast) node = k2.y;
+    else pop();
+}
+
+// Top-level leaf `leaf` (first | cnt << 24): its next instance, `id`; the rest of the range waits on the top-level stack.  `r` becomes the
+// ray instance `id` sees — o' = inv (o, 1), d' = inv (d, 0): ((m0 x + m1 y) + m2 z) + m3, left to right (-ffp-contract=off: nothing is
+// fused), with the ray's own minT and maxT whatever other instances have reported — and enter(id) starts the instance's traversal.  If
+// the closest-hit path rejects the transformed ray (not finite), h_id is a miss: reject().
+template <class Stack, class Reject, class Enter>
+__device__ __forceinline__ void worldEnterNext(const uint32_t* order, const float4* inv, uint32_t leaf, const WorldRay& w, Stack& top, LaneRay& r, Reject&& reject, Enter&& enter) {
+    const uint32_t first = leaf & 0xFFFFFFu, cnt = leaf >> 24;
+    const uint32_t id = order[first];
+    if (cnt > 1u) top.push(((cnt - 1u) << 24) | (first + 1u));
+    const float4 m0 = inv[size_t(id) * 3], m1 = inv[size_t(id) * 3 + 1], m2 = inv[size_t(id) * 3 + 2];
+    const float ox = ((m0.x * w.ox + m0.y * w.oy) + m0.z * w.oz) + m0.w;
+    const float oy = ((m1.x * w.ox + m1.y * w.oy) + m1.z * w.oz) + m1.w;
+    const float oz = ((m2.x * w.ox + m2.y * w.oy) + m2.z * w.oz) + m2.w;
+    const float dx = (m0.x * w.dx + m0.y * w.dy) + m0.z * w.dz;
+    const float dy = (m1.x * w.dx + m1.y * w.dy) + m1.z * w.dz;
+    const float dz = (m2.x * w.dx + m2.y * w.dy) + m2.z * w.dz;
+    if (!(isfinite(ox) && isfinite(oy) && isfinite(oz) && isfinite(dx) && isfinite(dy) && isfinite(dz))) reject();
+    else {
+        setLaneRay(r, ox, oy, oz, dx, dy, dz, w.tNear, w.tMax);
+        enter(id);
+    }
+}
+
 __global__ void __launch_bounds__(kWorldBlock) worldIntersectKernel(const WorldArgs a) {
     __shared__ uint32_t topLds[kWorldTopLds * kWorldBlock];
     __shared__ uint32_t botLds[kWorldBotLds * kWorldBlock];
@@ -88,9 +158,7 @@ __global__ void __launch_bounds__(kWorldBlock) worldIntersectKernel(const WorldA
     LaneStack<kWorldTopLds, kWorldBlock> top{topLds + tid, a.spillTop, a.topSpillLevels, a.spillStride, gtid, 0u};
     LaneStack<kWorldBotLds, kWorldBlock> bot{botLds + tid, a.spillBot, a.botSpillLevels, a.spillStride, gtid, 0u};
 
-    // the world ray: origin, direction as given (what the instances transform), 1/d of the clamped direction for the top-level boxes
-    float wox = 0.0f, woy = 0.0f, woz = 0.0f, wdx = 0.0f, wdy = 0.0f, wdz = 0.0f, wix = 0.0f, wiy = 0.0f, wiz = 0.0f;
-    float tNear = 0.0f, tMax = 0.0f, pad = 0.0f;
+    WorldRay w = {};      // the world ray
     // the best instance result so far (raw: pair index * 2 + which, unrotated barycentrics) and the limit the top level culls with
     float bestT = 0.0f, bestU = 0.0f, bestV = 0.0f, tCull = 0.0f;
     int bestIndex = -1;
@@ -134,12 +202,9 @@ __global__ void __launch_bounds__(kWorldBlock) worldIntersectKernel(const WorldA
                 a.results[idx] = make_float4(__uint_as_float(kInvalidTriangle), 0.0f, 0.0f, 0.0f);
                 a.instances[idx] = kWorldNoInst;
             } else {
-                wox = q0.x; woy = q0.y; woz = q0.z; tNear = q0.w;
-                wdx = q1.x; wdy = q1.y; wdz = q1.z; tMax = q1.w;
-                wix = 1.0f / clampDir(wdx); wiy = 1.0f / clampDir(wdy); wiz = 1.0f / clampDir(wdz);      // the clamp here only for the top-level box tests
-                pad = a.rayPad * (fabsf(wox) + fabsf(woy) + fabsf(woz));
+                setWorldRay(w, q0, q1, a.rayPad);
                 bestInst = kWorldNoInst; bestIndex = -1; bestT = bestU = bestV = 0.0f;
-                tCull = tMax;
+                tCull = w.tMax;
                 rayIdx = idx;
                 inst = kWorldNoInst;
                 node = 0x80000000u;      // the top-level root
@@ -169,46 +234,16 @@ __global__ void __launch_bounds__(kWorldBlock) worldIntersectKernel(const WorldA
             if (isBotInner && !bvh2InnerStep(scNodes, node, r, r.tFar, bot)) botPop();      // tRay = the current tFar
         } else if (nTop != 0u) {
             if (isTop) {
-                if (int(node) < 0) {      // top-level inner node: both child boxes, padded, against [tNear, widened best t]
-                    const float4* np = a.topNodes + size_t(node & 0x7FFFFFFFu) * 4;
-                    const uint2 k2 = *reinterpret_cast<const uint2*>(np);
-                    float4 d1 = np[1], d2 = np[2], d3 = np[3];
-                    d1.x -= pad; d1.y += pad; d1.z -= pad; d1.w += pad;
-                    d2.x -= pad; d2.y += pad; d2.z -= pad; d2.w += pad;
-                    d3.x -= pad; d3.y += pad; d3.z -= pad; d3.w += pad;
-                    const float tEnd = tCull + fmaxf(fabsf(tCull) * 9.5367431640625e-07f, 1e-30f);      // 2^-20 of itself: past every t that could still win or tie
-                    float tFirst, tLast;
-                    slabPair(d1, d2, d3, wix, wiy, wiz, -wox * wix, -woy * wiy, -woz * wiz, tNear, tEnd, tFirst, tLast);
-                    const bool hitFirst = tFirst != tEnd && !worldEmptyRef(k2.x);      // (slabPair: tEnd doubles as "missed")
-                    const bool hitLast = tLast != tEnd && !worldEmptyRef(k2.y);
-                    if (hitFirst && hitLast) {
-                        const bool lastNearer = tLast < tFirst;
-                        top.push(lastNearer ? k2.x : k2.y);
-                        node = lastNearer ? k2.y : k2.x;
-                    } else if (hitFirst) node = k2.x;
-                    else if (hitLast) node = k2.y;
-                    else topPop();
-                } else {                  // top-level leaf: enter its next instance (the rest of the range waits on the top-level stack)
-                    const uint32_t first = node & 0xFFFFFFu, cnt = node >> 24;
-                    const uint32_t id = a.order[first];
-                    if (cnt > 1u) top.push(((cnt - 1u) << 24) | (first + 1u));
-                    const float4 m0 = a.inv[size_t(id) * 3], m1 = a.inv[size_t(id) * 3 + 1], m2 = a.inv[size_t(id) * 3 + 2];
-                    // o' = inv (o, 1), d' = inv (d, 0): ((m0 x + m1 y) + m2 z) + m3, left to right (-ffp-contract=off: nothing is fused)
-                    const float ox = ((m0.x * wox + m0.y * woy) + m0.z * woz) + m0.w;
-                    const float oy = ((m1.x * wox + m1.y * woy) + m1.z * woz) + m1.w;
-                    const float oz = ((m2.x * wox + m2.y * woy) + m2.z * woz) + m2.w;
-                    const float dx = (m0.x * wdx + m0.y * wdy) + m0.z * wdz;
-                    const float dy = (m1.x * wdx + m1.y * wdy) + m1.z * wdz;
-                    const float dz = (m2.x * wdx + m2.y * wdy) + m2.z * wdz;
-                    if (!(isfinite(ox) && isfinite(oy) && isfinite(oz) && isfinite(dx) && isfinite(dy) && isfinite(dz))) topPop();      // the closest-hit path rejects this ray: h_i is a miss
-                    else {
-                        setLaneRay(r, ox, oy, oz, dx, dy, dz, tNear, tMax);      // the ray's own maxT, whatever the other instances have reported
+                if (int(node) < 0) {      // top-level inner node, against [tNear, widened best t]: past every t that could still win or tie
+                    worldTopInnerStep(a.topNodes, node, w, worldWidenedEnd(tCull), top, topPop);
+                } else {                  // top-level leaf: enter its next instance
+                    worldEnterNext(a.order, a.inv, node, w, top, r, topPop, [&](uint32_t id) {
                         const WorldInstDev e = a.table[id];
                         scNodes = e.nodes; scPairs = e.pairs;
                         inst = id;
                         node = 0x80000000u;     // Kernels.h:164
                         bot.height = 0u;
-                    }
+                    });
                 }
             }
         }
@@ -281,32 +316,41 @@ int worldCommit(racc_hip_world* w, const float* transforms12) try {
     return fail(RACC_HIP_ERR_NOMEM, "world: out of host memory");
 }
 
-// Enqueues one world launch on `st` (scratch: racc_query.inc; here the cursor word and both spills).
-int launchWorld(racc_hip_ctx* ctx, const racc_hip_world* w, const void* dRays, void* dResults, uint32_t* dInstances, uint32_t count, hipStream_t st) {
-    // RACC_WORLD_WAVES / RACC_WORLD_REFILL / RACC_WORLD_LEAF: A/B of the grid size and the two vote thresholds (tools/bench_world.py)
-    static const uint32_t envWaves = queryTunable("RACC_WORLD_WAVES", 1, 8, kWorldWavesPerSimd);
-    static const uint32_t envRefill = queryTunable("RACC_WORLD_REFILL", 1, 64, kWorldRefillMin);
-    static const uint32_t envLeaf = queryTunable("RACC_WORLD_LEAF", 1, 64, kWorldLeafMin);
+// What a launch of either world kernel does on the host: the grid and the feed, the members the two argument structs share (same names),
+// and launch(a, blocks) inside the launch's scratch (racc_query.inc; here the cursor word and both spills).
+template <class Args, class Launch>
+int launchOnWorld(racc_hip_ctx* ctx, const racc_hip_world* w, const void* dRays, uint32_t count, uint32_t waves, uint32_t refillMin, uint32_t leafMin,
+                  const char* limitMsg, const char* launchMsg, hipStream_t st, Args& a, Launch&& launch) {
     QueryGrid g;
-    WorldArgs a;
-    if (int rc = queryGrid(ctx, count, uint32_t(kWorldBlock), envWaves, "world_intersect: more than 0xFF000000 rays in one launch", g, a.feed)) return rc;
+    if (int rc = queryGrid(ctx, count, uint32_t(kWorldBlock), waves, limitMsg, g, a.feed)) return rc;
     a.rays = static_cast<const float4*>(dRays);
-    a.results = static_cast<float4*>(dResults);
-    a.instances = dInstances;
     a.topNodes = w->topNodes; a.order = w->order; a.inv = w->inv; a.table = w->table;
     a.rayPad = w->rayPad;
     a.topSpillLevels = w->info.spill_levels;
     a.botSpillLevels = w->info.bottom_spill_levels;
     a.spillStride = g.gridThreads;
-    a.feed.refillMin = envRefill; a.leafMin = envLeaf;
+    a.feed.refillMin = refillMin; a.leafMin = leafMin;
     a.maxIters = ctx->maxIters;
     a.trips = ctx->devTrips;
-    return withQueryScratch(size_t(a.topSpillLevels + a.botSpillLevels) * g.gridThreads, st, "launch worldIntersectKernel", [&](uint32_t* scratch) {
+    return withQueryScratch(size_t(a.topSpillLevels + a.botSpillLevels) * g.gridThreads, st, launchMsg, [&](uint32_t* scratch) {
         a.feed.cursor = scratch;
         a.spillTop = scratch + kQueryScratchHead;
         a.spillBot = a.spillTop + size_t(a.topSpillLevels) * g.gridThreads;
-        hipLaunchKernelGGL(worldIntersectKernel, dim3(g.blocks), dim3(kWorldBlock), 0, st, a);
+        launch(a, g.blocks);
     });
+}
+
+// Enqueues one world launch on `st`.
+int launchWorld(racc_hip_ctx* ctx, const racc_hip_world* w, const void* dRays, void* dResults, uint32_t* dInstances, uint32_t count, hipStream_t st) {
+    // RACC_WORLD_WAVES / RACC_WORLD_REFILL / RACC_WORLD_LEAF: A/B of the grid size and the two vote thresholds (tools/bench_world.py)
+    static const uint32_t envWaves = queryTunable("RACC_WORLD_WAVES", 1, 8, kWorldWavesPerSimd);
+    static const uint32_t envRefill = queryTunable("RACC_WORLD_REFILL", 1, 64, kWorldRefillMin);
+    static const uint32_t envLeaf = queryTunable("RACC_WORLD_LEAF", 1, 64, kWorldLeafMin);
+    WorldArgs a;
+    a.results = static_cast<float4*>(dResults);
+    a.instances = dInstances;
+    return launchOnWorld(ctx, w, dRays, count, envWaves, envRefill, envLeaf, "world_intersect: more than 0xFF000000 rays in one launch", "launch worldIntersectKernel", st, a,
+                         [&](const WorldArgs& args, uint32_t blocks) { hipLaunchKernelGGL(worldIntersectKernel, dim3(blocks), dim3(kWorldBlock), 0, st, args); });
 }
 
 }  // namespace

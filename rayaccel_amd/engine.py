@@ -101,6 +101,8 @@ ABI = {
     "racc_hip_world_get_info": (_i, [_vp, _P(WorldInfo)]),
     "racc_hip_world_intersect_device": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     "racc_hip_world_intersect": (_i, [_vp, _vp, _vp, _vp, _vp, _u32]),
+    "racc_hip_world_occluded_device": (_i, [_vp, _vp, _vp, _vp, _u32, _vp]),
+    "racc_hip_world_occluded": (_i, [_vp, _vp, _vp, _vp, _u32]),
     "racc_hip_get_launch_info": (_i, [_vp, _u32, _P(LaunchInfo)]),
     "racc_hip_read_kernel_times": (_i, [_vp, _u32, _P(C.c_float), _u32, _P(_u32)]),
     "racc_hip_read_stats": (_i, [_vp, _u32, _P(_u64), _i]),
@@ -357,6 +359,22 @@ class World:
         """Device-resident form (racc_hip_world_intersect_device): asynchronous on `stream` (None = the default stream), complete after
         Context.stream_synchronize(stream)."""
         _check(load_library().racc_hip_world_intersect_device(self._ctx._h, self._h, d_rays, d_results, d_instances, count, stream))
+
+    def occluded(self, rays, out=None):
+        """Host Ray[N] in, np.uint8[N] out (1 = some instance has something in (minT, maxT]: exactly where intersect reports an instance),
+        blocking (racc_hip_world_occluded)."""
+        rays = np.ascontiguousarray(rays)
+        assert rays.dtype.itemsize == 32
+        if out is None:
+            out = np.zeros(len(rays), np.uint8)
+        assert out.dtype == np.uint8 and out.flags.c_contiguous and len(out) >= len(rays)
+        _check(load_library().racc_hip_world_occluded(self._ctx._h, self._h, _ptr(rays), _ptr(out), len(rays)))
+        return out
+
+    def occluded_device(self, d_rays, d_out, count, stream=None):
+        """Device-resident form (racc_hip_world_occluded_device): asynchronous on `stream` (None = the default stream), complete after
+        Context.stream_synchronize(stream)."""
+        _check(load_library().racc_hip_world_occluded_device(self._ctx._h, self._h, d_rays, d_out, count, stream))
 
     def update(self, transforms):
         """New transforms for the same scenes — also the call to make after a member scene was refitted.  Blocking (racc_hip_world_update)."""
