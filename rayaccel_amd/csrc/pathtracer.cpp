@@ -31,6 +31,7 @@
 #include <cstring>
 #include <thread>
 #include <vector>
+#include <xmmintrin.h>
 
 extern "C" {
 
@@ -252,6 +253,54 @@ extern "C" long long racc_pt_test_shade8(uint32_t n, uint32_t seed, uint32_t* al
     (void)n; (void)seed; if (alive_count) *alive_count = 0;
     return -1;
 #endif
+}
+// Test hook: ptshade::primaryRay over n (x, y, pixel, sample) — cam = origin, right, up, view (12 floats); rays_out RayRec[n], paths_out PathRec[n].
+// No GPU context.  (tests/test_pt_reference.py holds it to oracle/pt_reference.py; tests/test_gpu_pt_kernels.py holds ptGenKernel to it.)
+extern "C" void racc_pt_test_primary_rays(const float* cam, const uint32_t* x, const uint32_t* y, const uint32_t* pixel, const uint32_t* sample, uint32_t n,
+                                          void* rays_out, void* paths_out) {
+    ptshade::Camera c{{cam[0], cam[1], cam[2]}, {cam[3], cam[4], cam[5]}, {cam[6], cam[7], cam[8]}, {cam[9], cam[10], cam[11]}};
+    ptshade::RayRec* rays = static_cast<ptshade::RayRec*>(rays_out);
+    LightPath* paths = static_cast<LightPath*>(paths_out);
+    for (uint32_t i = 0; i < n; ++i) ptshade::primaryRay(c, x[i], y[i], pixel[i], sample[i], rays[i], paths[i]);
+}
+// Test hook: what one shading pass does with n records (ray, hit, payload, sample index) a test supplies, UNCOMPACTED (output i belongs to
+// input i).  A miss -> missContribution into contrib[3i..] / valid[3i..]; otherwise the depth and triangle guard, then shadeSurface on the
+// record's ShadeTri (tris[hit.triangle]) -> alive[i], rays_out[i], paths_out[i] (zero where the path ends).  materials = ptshade::Materials
+// (kd[4][3], eta[4]: 16 floats).  The render threads shade with FTZ/DAZ set (Threading.h:78-79) and the device build flushes denormals: the
+// hook sets the same mode for its duration and restores the caller's.  No GPU context.  Returns 0, or -1 for a material index above 3.
+extern "C" int racc_pt_test_shade(const void* tris_in, uint32_t triangleCount, const float* materials, uint32_t maxDepth,
+                                   const void* rays_in, const void* hits_in, const void* paths_in, const uint32_t* samples, uint32_t n,
+                                   int32_t* alive, void* rays_out, void* paths_out, long long* contrib, uint8_t* valid) {
+    const ptshade::ShadeTri* tris = static_cast<const ptshade::ShadeTri*>(tris_in);
+    const ptshade::RayRec* rays = static_cast<const ptshade::RayRec*>(rays_in);
+    const ptshade::HitRec* hits = static_cast<const ptshade::HitRec*>(hits_in);
+    const LightPath* paths = static_cast<const LightPath*>(paths_in);
+    ptshade::RayRec* nextRays = static_cast<ptshade::RayRec*>(rays_out);
+    LightPath* nextPaths = static_cast<LightPath*>(paths_out);
+    ptshade::Materials mat;
+    std::memcpy(&mat, materials, sizeof(mat));
+    for (uint32_t t = 0; t < triangleCount; ++t) if (tris[t].material > 3u) return -1;      // (the material table has four rows)
+    const unsigned csr = _mm_getcsr();
+    _mm_setcsr(csr | 0x8040u);                       // FTZ | DAZ
+    for (uint32_t i = 0; i < n; ++i) {
+        alive[i] = 0;
+        std::memset(&nextRays[i], 0, sizeof(nextRays[i])); std::memset(&nextPaths[i], 0, sizeof(nextPaths[i]));
+        for (int ch = 0; ch < 3; ++ch) { contrib[3 * size_t(i) + ch] = 0; valid[3 * size_t(i) + ch] = 0; }
+        if (hits[i].triangle == racc::invalidTriangle) {
+            long long add[3]; bool ok[3];
+            ptshade::missContribution(hits[i], paths[i], add, ok);
+            for (int ch = 0; ch < 3; ++ch) { contrib[3 * size_t(i) + ch] = add[ch]; valid[3 * size_t(i) + ch] = ok[ch] ? 1 : 0; }
+            continue;
+        }
+        if ((paths[i].pixelDepth >> 24) >= maxDepth || hits[i].triangle >= triangleCount) continue;
+        const ptshade::ShadeTri& st = tris[hits[i].triangle];
+        ptshade::RayRec nr; LightPath np;
+        if (ptshade::shadeSurface(mat, rays[i], hits[i], paths[i], samples[i], st.n0, st.n1, st.n2, ptshade::Vec{st.ng[0], st.ng[1], st.ng[2]}, st.material, nr, np)) {
+            alive[i] = 1; nextRays[i] = nr; nextPaths[i] = np;
+        }
+    }
+    _mm_setcsr(csr);
+    return 0;
 }
 extern "C" void racc_pt_test_uniform(uint32_t pixel, uint32_t sample, uint32_t depth, uint32_t stream, uint32_t n, float* out) {
     for (uint32_t i = 0; i < n; ++i) out[i] = ptshade::uniformKeyed(ptshade::pathKey(pixel + i, sample), depth, stream);

@@ -10,7 +10,8 @@
 //             write the next ray through a workgroup-aggregated (ballots + LDS + one atomic per 1024 rays) compaction   (…Renderer.cpp:72-566)
 // until no path is alive.  The per-ray arithmetic is pt_shade.h, the same source the host consumer compiles, the RNG is
 // keyed by (pixel, sample, depth) and the frame buffer is integer, so both consumers render the SAME image bit for bit
-// (tests/test_gpu_pathtracer.py) — the host consumer is this kernel's oracle.
+// (tests/test_gpu_pathtracer.py) — the host consumer is this kernel's oracle, and both are held to oracle/pt_reference.py (a float64
+// restatement of the reference's lines) record by record: tests/test_pt_reference.py, tests/test_gpu_pt_kernels.py.
 // Compiled with -fgpu-flush-denormals-to-zero: the host callbacks run with FTZ/DAZ set (Threading.h:78-79).
 
 #include <hip/hip_runtime.h>
@@ -22,6 +23,7 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 extern "C" {
@@ -48,13 +50,30 @@ int racc_ptdev_render_file(const char* scene_bin, int device, uint32_t width, ui
 // of each — to the two host arrays (Ray 32 B, Result 16 B), so that a test can re-trace exactly what the device consumer traced
 // with the oracle.  *count = records copied (0 if the render had fewer rounds).  One-shot; capacity 0 disarms.
 void racc_ptdev_capture_round(uint32_t round, void* rays_out, void* hits_out, uint32_t capacity, uint32_t* count);
+// The same, and also the payloads (PathRec 16 B) and sample indices (uint32) that round's ptShadeKernel launch is handed with those rays and hits.
+void racc_ptdev_capture_round_paths(uint32_t round, void* rays_out, void* hits_out, void* paths_out, uint32_t* samples_out, uint32_t capacity, uint32_t* count);
+
+// Test hooks: the two kernels on arrays a test supplies, launched as the render loop launches them (tests/test_gpu_pt_kernels.py).
+// Compute units of `device` (hipDeviceProp_t::multiProcessorCount, what both grid rules below are sized by), or a negative error code.
+int racc_ptdev_compute_units(int device);
+// One ptGenKernel launch, grid min(ceil(n / 256), CUs * 8), n = regionW * regionH * samples; the three outputs hold n records.  cam = origin,
+// right, up, view (12 floats); regionW and regionH are multiples of 8 (the kernel walks 8x8 blocks).  Returns 0 on success.
+int racc_ptdev_test_gen(int device, const float* cam, uint32_t width, uint32_t regionW, uint32_t regionH, uint32_t sampleFirst, uint32_t samples,
+                        void* rays_out, void* paths_out, uint32_t* sample_out);
+// One ptShadeKernel launch over `count` records, grid min(ceil(count / 1024), CUs * 2), on a zeroed survivor count and a zeroed frame of
+// frame_words 64-bit words: the compacted survivors (at most count), their number and the frame come back.  tris = ShadeTri[triangleCount]
+// (material 0..3), materials = ptshade::Materials (16 floats).  Every miss record's pixel must lie inside the frame (pixel * 3 + 2 <
+// frame_words), otherwise nothing is launched and -1 is returned.  Returns 0 on success.
+int racc_ptdev_test_shade(int device, const void* tris, uint32_t triangleCount, const float* materials, uint32_t maxDepth,
+                          const void* rays, const void* hits, const void* paths, const uint32_t* samples, uint32_t count,
+                          void* out_rays, void* out_paths, uint32_t* out_samples, uint32_t* out_count, long long* frame, uint64_t frame_words);
 }
 
 namespace {
 
 using namespace ptshade;
 
-struct Capture { uint32_t round = 0; void* rays = nullptr; void* hits = nullptr; uint32_t capacity = 0; uint32_t* count = nullptr; } g_capture;
+struct Capture { uint32_t round = 0; void* rays = nullptr; void* hits = nullptr; uint32_t capacity = 0; uint32_t* count = nullptr; void* paths = nullptr; uint32_t* samples = nullptr; } g_capture;
 
 // Pixels are walked in 8x8 blocks so that the 64 rays of a wave start out as one coherent bundle.
 __global__ void __launch_bounds__(256) ptGenKernel(Camera cam, uint32_t width, uint32_t regionW, uint32_t regionH,
@@ -138,8 +157,128 @@ __global__ void __launch_bounds__(kShadeBlock) ptShadeKernel(const ShadeTri* tri
 }  // namespace
 
 extern "C" void racc_ptdev_capture_round(uint32_t round, void* rays_out, void* hits_out, uint32_t capacity, uint32_t* count) {
-    g_capture = Capture{round, rays_out, hits_out, (rays_out && hits_out) ? capacity : 0u, count};
+    g_capture = Capture{round, rays_out, hits_out, (rays_out && hits_out) ? capacity : 0u, count, nullptr, nullptr};
     if (count) *count = 0;
+}
+
+extern "C" void racc_ptdev_capture_round_paths(uint32_t round, void* rays_out, void* hits_out, void* paths_out, uint32_t* samples_out, uint32_t capacity, uint32_t* count) {
+    g_capture = Capture{round, rays_out, hits_out, (rays_out && hits_out && paths_out && samples_out) ? capacity : 0u, count, paths_out, samples_out};
+    if (count) *count = 0;
+}
+
+#define PT_TEST_HIP(call)                                                                                        \
+    do {                                                                                                         \
+        hipError_t e_ = (call);                                                                                  \
+        if (e_ != hipSuccess) { std::fprintf(stderr, "racc_ptdev: %s: %s\n", #call, hipGetErrorString(e_)); rc = -4; goto done; } \
+    } while (0)
+
+extern "C" int racc_ptdev_compute_units(int device) {
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return -4;
+    return prop.multiProcessorCount;
+}
+
+extern "C" int racc_ptdev_test_gen(int device, const float* cam, uint32_t width, uint32_t regionW, uint32_t regionH, uint32_t sampleFirst, uint32_t samples,
+                                   void* rays_out, void* paths_out, uint32_t* sample_out) {
+    if (!cam || !rays_out || !paths_out || !sample_out || !regionW || !regionH || !samples || (regionW & 7u) || (regionH & 7u) || width < regionW) return -1;
+    const uint64_t total = uint64_t(regionW) * regionH * samples;
+    if (total > (1ull << 30) || uint64_t(width) * regionH > (1u << 24)) return -1;      // 32-bit ray counts; 24-bit pixel index (as racc_ptdev_render_file)
+    const uint32_t n = uint32_t(total);
+    const Camera c{{cam[0], cam[1], cam[2]}, {cam[3], cam[4], cam[5]}, {cam[6], cam[7], cam[8]}, {cam[9], cam[10], cam[11]}};
+    int rc = 0;
+    RayRec* dRays = nullptr; PathRec* dPaths = nullptr; uint32_t* dSample = nullptr;
+    hipDeviceProp_t prop;
+    PT_TEST_HIP(hipSetDevice(device));
+    PT_TEST_HIP(hipGetDeviceProperties(&prop, device));
+    PT_TEST_HIP(hipMalloc(&dRays, size_t(n) * sizeof(RayRec)));
+    PT_TEST_HIP(hipMalloc(&dPaths, size_t(n) * sizeof(PathRec)));
+    PT_TEST_HIP(hipMalloc(&dSample, size_t(n) * 4));
+    {
+        const uint32_t maxBlocks = uint32_t(prop.multiProcessorCount) * 8u;      // the render loop's rule
+        const uint32_t blocks = (n + 255u) / 256u < maxBlocks ? (n + 255u) / 256u : maxBlocks;
+        hipLaunchKernelGGL(ptGenKernel, dim3(blocks), dim3(256), 0, nullptr, c, width, regionW, regionH, sampleFirst, samples, dRays, dPaths, dSample);
+    }
+    PT_TEST_HIP(hipGetLastError());
+    PT_TEST_HIP(hipDeviceSynchronize());
+    PT_TEST_HIP(hipMemcpy(rays_out, dRays, size_t(n) * sizeof(RayRec), hipMemcpyDeviceToHost));
+    PT_TEST_HIP(hipMemcpy(paths_out, dPaths, size_t(n) * sizeof(PathRec), hipMemcpyDeviceToHost));
+    PT_TEST_HIP(hipMemcpy(sample_out, dSample, size_t(n) * 4, hipMemcpyDeviceToHost));
+done:
+    if (rc != 0) hipDeviceSynchronize();
+    if (dRays) hipFree(dRays);
+    if (dPaths) hipFree(dPaths);
+    if (dSample) hipFree(dSample);
+    return rc;
+}
+
+extern "C" int racc_ptdev_test_shade(int device, const void* tris, uint32_t triangleCount, const float* materials, uint32_t maxDepth,
+                                     const void* rays, const void* hits, const void* paths, const uint32_t* samples, uint32_t count,
+                                     void* out_rays, void* out_paths, uint32_t* out_samples, uint32_t* out_count, long long* frame, uint64_t frame_words) {
+    if (!tris || !triangleCount || !materials || !rays || !hits || !paths || !samples || !count || !out_rays || !out_paths || !out_samples || !out_count ||
+        !frame || !frame_words || count > (1u << 30)) return -1;
+    {   // nothing a record says may reach outside the buffers: a miss adds to frame[pixel * 3 + ch]; a hit reads mat.kd[material]
+        const HitRec* h = static_cast<const HitRec*>(hits);
+        const PathRec* p = static_cast<const PathRec*>(paths);
+        for (uint32_t i = 0; i < count; ++i)
+            if (h[i].triangle == 0xFFFFFFFFu && uint64_t(p[i].pixelDepth & 0xFFFFFFu) * 3u + 2u >= frame_words) return -1;
+        const ShadeTri* t = static_cast<const ShadeTri*>(tris);
+        for (uint32_t i = 0; i < triangleCount; ++i) if (t[i].material > 3u) return -1;
+    }
+    Materials mat;
+    std::memcpy(&mat, materials, sizeof(mat));
+    int rc = 0;
+    ShadeTri* dTris = nullptr; RayRec* dRays = nullptr; HitRec* dHits = nullptr; PathRec* dPaths = nullptr; uint32_t* dSample = nullptr;
+    RayRec* dOutRays = nullptr; PathRec* dOutPaths = nullptr; uint32_t* dOutSample = nullptr; uint32_t* dCount = nullptr; unsigned long long* dFrame = nullptr;
+    uint32_t survivors = 0;
+    hipDeviceProp_t prop;
+    PT_TEST_HIP(hipSetDevice(device));
+    PT_TEST_HIP(hipGetDeviceProperties(&prop, device));
+    PT_TEST_HIP(hipMalloc(&dTris, size_t(triangleCount) * sizeof(ShadeTri)));
+    PT_TEST_HIP(hipMalloc(&dRays, size_t(count) * sizeof(RayRec)));
+    PT_TEST_HIP(hipMalloc(&dHits, size_t(count) * sizeof(HitRec)));
+    PT_TEST_HIP(hipMalloc(&dPaths, size_t(count) * sizeof(PathRec)));
+    PT_TEST_HIP(hipMalloc(&dSample, size_t(count) * 4));
+    PT_TEST_HIP(hipMalloc(&dOutRays, size_t(count) * sizeof(RayRec)));
+    PT_TEST_HIP(hipMalloc(&dOutPaths, size_t(count) * sizeof(PathRec)));
+    PT_TEST_HIP(hipMalloc(&dOutSample, size_t(count) * 4));
+    PT_TEST_HIP(hipMalloc(&dCount, 4));
+    PT_TEST_HIP(hipMalloc(&dFrame, size_t(frame_words) * 8));
+    PT_TEST_HIP(hipMemcpy(dTris, tris, size_t(triangleCount) * sizeof(ShadeTri), hipMemcpyHostToDevice));
+    PT_TEST_HIP(hipMemcpy(dRays, rays, size_t(count) * sizeof(RayRec), hipMemcpyHostToDevice));
+    PT_TEST_HIP(hipMemcpy(dHits, hits, size_t(count) * sizeof(HitRec), hipMemcpyHostToDevice));
+    PT_TEST_HIP(hipMemcpy(dPaths, paths, size_t(count) * sizeof(PathRec), hipMemcpyHostToDevice));
+    PT_TEST_HIP(hipMemcpy(dSample, samples, size_t(count) * 4, hipMemcpyHostToDevice));
+    PT_TEST_HIP(hipMemset(dCount, 0, 4));
+    PT_TEST_HIP(hipMemset(dFrame, 0, size_t(frame_words) * 8));
+    PT_TEST_HIP(hipDeviceSynchronize());
+    {
+        const uint32_t need = (count + uint32_t(kShadeBlock) - 1u) / uint32_t(kShadeBlock);      // the render loop's rule
+        const uint32_t blocks = need < uint32_t(prop.multiProcessorCount) * 2u ? need : uint32_t(prop.multiProcessorCount) * 2u;
+        hipLaunchKernelGGL(ptShadeKernel, dim3(blocks), dim3(kShadeBlock), 0, nullptr, dTris, triangleCount, mat, maxDepth, dRays, dHits, dPaths, dSample, count,
+                           dOutRays, dOutPaths, dOutSample, dCount, dFrame);
+    }
+    PT_TEST_HIP(hipGetLastError());
+    PT_TEST_HIP(hipDeviceSynchronize());
+    PT_TEST_HIP(hipMemcpy(&survivors, dCount, 4, hipMemcpyDeviceToHost));
+    *out_count = survivors;
+    if (survivors > count) { std::fprintf(stderr, "racc_ptdev: %u survivors of %u records\n", survivors, count); rc = -5; goto done; }
+    PT_TEST_HIP(hipMemcpy(out_rays, dOutRays, size_t(survivors) * sizeof(RayRec), hipMemcpyDeviceToHost));
+    PT_TEST_HIP(hipMemcpy(out_paths, dOutPaths, size_t(survivors) * sizeof(PathRec), hipMemcpyDeviceToHost));
+    PT_TEST_HIP(hipMemcpy(out_samples, dOutSample, size_t(survivors) * 4, hipMemcpyDeviceToHost));
+    PT_TEST_HIP(hipMemcpy(frame, dFrame, size_t(frame_words) * 8, hipMemcpyDeviceToHost));
+done:
+    if (rc != 0) hipDeviceSynchronize();
+    if (dTris) hipFree(dTris);
+    if (dRays) hipFree(dRays);
+    if (dHits) hipFree(dHits);
+    if (dPaths) hipFree(dPaths);
+    if (dSample) hipFree(dSample);
+    if (dOutRays) hipFree(dOutRays);
+    if (dOutPaths) hipFree(dOutPaths);
+    if (dOutSample) hipFree(dOutSample);
+    if (dCount) hipFree(dCount);
+    if (dFrame) hipFree(dFrame);
+    return rc;
 }
 
 extern "C" int racc_ptdev_render_file(const char* scene_bin, int device, uint32_t width, uint32_t height,
@@ -236,6 +375,8 @@ extern "C" int racc_ptdev_render_file(const char* scene_bin, int device, uint32_
                 if (racc_hip_stream_synchronize(ctx, P.stream) != RACC_HIP_OK) return -3;
                 if (hipMemcpy(g_capture.rays, P.rays[P.cur], size_t(n) * sizeof(RayRec), hipMemcpyDeviceToHost) != hipSuccess) return -4;
                 if (hipMemcpy(g_capture.hits, P.hits, size_t(n) * sizeof(HitRec), hipMemcpyDeviceToHost) != hipSuccess) return -4;
+                if (g_capture.paths && hipMemcpy(g_capture.paths, P.paths[P.cur], size_t(n) * sizeof(PathRec), hipMemcpyDeviceToHost) != hipSuccess) return -4;
+                if (g_capture.samples && hipMemcpy(g_capture.samples, P.sample[P.cur], size_t(n) * 4, hipMemcpyDeviceToHost) != hipSuccess) return -4;
                 if (g_capture.count) *g_capture.count = n;
                 g_capture.capacity = 0;
             }

@@ -756,6 +756,122 @@ def path_trace_capture_round(round_index, capacity):
     return rays, hits, count
 
 
+PATH_DTYPE = np.dtype([("weight", "<f4", 3), ("pixelDepth", "<u4")])       # the path payload (ptshade::PathRec): weight + pixel (low 24 bits) | depth << 24
+SHADE_TRI_DTYPE = np.dtype([("n0", "<f4", 3), ("n1", "<f4", 3), ("n2", "<f4", 3), ("ng", "<f4", 3), ("material", "<u4"), ("pad", "<u4", 3)])      # ptshade::ShadeTri
+assert PATH_DTYPE.itemsize == 16 and SHADE_TRI_DTYPE.itemsize == 64
+
+
+def path_trace_capture_round_paths(round_index, capacity):
+    """path_trace_capture_round, and also the payloads and sample indices the shading kernel is handed in that round
+    (racc_ptdev_capture_round_paths).  Returns (rays, hits, paths, samples, count)."""
+    lib = C.CDLL(PTDEV_LIB_PATH)
+    rays, hits, count = np.zeros(capacity, RAY_DTYPE), np.zeros(capacity, RESULT_DTYPE), C.c_uint32(0)
+    paths, samples = np.zeros(capacity, PATH_DTYPE), np.zeros(capacity, np.uint32)
+    lib.racc_ptdev_capture_round_paths.restype = None
+    lib.racc_ptdev_capture_round_paths.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+    lib.racc_ptdev_capture_round_paths(round_index, _ptr(rays), _ptr(hits), _ptr(paths), _ptr(samples), capacity, C.byref(count))
+    return rays, hits, paths, samples, count
+
+
+def _pt_materials(materials):
+    """dict(kd=[4,3], eta=[4]) -> the 16 floats of ptshade::Materials."""
+    return np.ascontiguousarray(np.concatenate([np.asarray(materials["kd"], np.float32).reshape(12), np.asarray(materials["eta"], np.float32).reshape(4)]))
+
+
+def _pt_records(rays, hits, paths, samples):
+    rays, hits, paths = np.ascontiguousarray(rays), np.ascontiguousarray(hits), np.ascontiguousarray(paths)
+    samples = np.ascontiguousarray(samples, np.uint32)
+    if rays.dtype != RAY_DTYPE or hits.dtype != RESULT_DTYPE or paths.dtype != PATH_DTYPE or not (len(rays) == len(hits) == len(paths) == len(samples)):
+        raise ValueError("rays / hits / paths / samples: RAY_DTYPE, RESULT_DTYPE, PATH_DTYPE, uint32 of one length")
+    return rays, hits, paths, samples
+
+
+def pt_host_primary_rays(cam, x, y, pixel, sample):
+    """Test hook (racc_pt_test_primary_rays, no GPU): the host consumer's camera ray for every (x, y, pixel, sample).
+    cam: 12 floats = origin, right, up, view.  Returns (rays RAY_DTYPE, paths PATH_DTYPE)."""
+    lib = C.CDLL(PT_LIB_PATH)
+    cam = np.ascontiguousarray(cam, np.float32).reshape(12)
+    x, y, pixel, sample = (np.ascontiguousarray(a, np.uint32) for a in (x, y, pixel, sample))
+    n = len(x)
+    assert len(y) == len(pixel) == len(sample) == n
+    rays, paths = np.zeros(n, RAY_DTYPE), np.zeros(n, PATH_DTYPE)
+    lib.racc_pt_test_primary_rays.restype = None
+    lib.racc_pt_test_primary_rays.argtypes = [C.c_void_p] * 5 + [C.c_uint32, C.c_void_p, C.c_void_p]
+    lib.racc_pt_test_primary_rays(_ptr(cam), _ptr(x), _ptr(y), _ptr(pixel), _ptr(sample), n, _ptr(rays), _ptr(paths))
+    return rays, paths
+
+
+def pt_host_shade(tris, materials, max_depth, rays, hits, paths, samples):
+    """Test hook (racc_pt_test_shade, no GPU): one shading pass of the host consumer over the records, uncompacted.
+    Returns dict(alive bool[n], rays, paths, contrib int64[n,3], valid bool[n,3]) — output i belongs to input i."""
+    lib = C.CDLL(PT_LIB_PATH)
+    tris = np.ascontiguousarray(tris)
+    assert tris.dtype == SHADE_TRI_DTYPE and len(tris) > 0
+    rays, hits, paths, samples = _pt_records(rays, hits, paths, samples)
+    mat = _pt_materials(materials)
+    n = len(rays)
+    alive, out_rays, out_paths = np.zeros(n, np.int32), np.zeros(n, RAY_DTYPE), np.zeros(n, PATH_DTYPE)
+    contrib, valid = np.zeros((n, 3), np.int64), np.zeros((n, 3), np.uint8)
+    lib.racc_pt_test_shade.restype = C.c_int
+    lib.racc_pt_test_shade.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 5
+    rc = lib.racc_pt_test_shade(_ptr(tris), len(tris), _ptr(mat), max_depth, _ptr(rays), _ptr(hits), _ptr(paths), _ptr(samples), n,
+                                _ptr(alive), _ptr(out_rays), _ptr(out_paths), _ptr(contrib), _ptr(valid))
+    if rc != 0:
+        raise RaccError(rc, "racc_pt_test_shade refused its input")
+    return dict(alive=alive != 0, rays=out_rays, paths=out_paths, contrib=contrib, valid=valid != 0)
+
+
+def pt_device_compute_units(device=0):
+    """Compute units of the device (racc_ptdev_compute_units): what the two kernels' grids are sized by."""
+    load_library()
+    lib = C.CDLL(PTDEV_LIB_PATH)
+    lib.racc_ptdev_compute_units.restype = C.c_int
+    lib.racc_ptdev_compute_units.argtypes = [C.c_int]
+    n = lib.racc_ptdev_compute_units(device)
+    if n <= 0:
+        raise RaccError(n, "racc_ptdev_compute_units failed")
+    return n
+
+
+def pt_device_gen(cam, width, region_w, region_h, sample_first, samples, device=0):
+    """Test hook (racc_ptdev_test_gen): one ptGenKernel launch with the render loop's grid.  Returns (rays, paths, sample index)
+    in the kernel's output order."""
+    load_library()
+    lib = C.CDLL(PTDEV_LIB_PATH)
+    cam = np.ascontiguousarray(cam, np.float32).reshape(12)
+    n = region_w * region_h * samples
+    rays, paths, sidx = np.zeros(n, RAY_DTYPE), np.zeros(n, PATH_DTYPE), np.zeros(n, np.uint32)
+    lib.racc_ptdev_test_gen.restype = C.c_int
+    lib.racc_ptdev_test_gen.argtypes = [C.c_int, C.c_void_p] + [C.c_uint32] * 5 + [C.c_void_p] * 3
+    rc = lib.racc_ptdev_test_gen(device, _ptr(cam), width, region_w, region_h, sample_first, samples, _ptr(rays), _ptr(paths), _ptr(sidx))
+    if rc != 0:
+        raise RaccError(rc, "racc_ptdev_test_gen failed")
+    return rays, paths, sidx
+
+
+def pt_device_shade(tris, materials, max_depth, rays, hits, paths, samples, frame_words, device=0):
+    """Test hook (racc_ptdev_test_shade): one ptShadeKernel launch with the render loop's grid on a zeroed count and frame.
+    Returns dict(count, rays, paths, samples — the compacted survivors — and frame int64[frame_words])."""
+    load_library()
+    lib = C.CDLL(PTDEV_LIB_PATH)
+    tris = np.ascontiguousarray(tris)
+    assert tris.dtype == SHADE_TRI_DTYPE and len(tris) > 0
+    rays, hits, paths, samples = _pt_records(rays, hits, paths, samples)
+    mat = _pt_materials(materials)
+    n = len(rays)
+    out_rays, out_paths, out_samples = np.zeros(n, RAY_DTYPE), np.zeros(n, PATH_DTYPE), np.zeros(n, np.uint32)
+    frame, count = np.zeros(frame_words, np.int64), C.c_uint32(0)
+    lib.racc_ptdev_test_shade.restype = C.c_int
+    lib.racc_ptdev_test_shade.argtypes = ([C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32] + [C.c_void_p] * 4 + [C.c_uint32] + [C.c_void_p] * 3 +
+                                          [C.POINTER(C.c_uint32), C.c_void_p, C.c_uint64])
+    rc = lib.racc_ptdev_test_shade(device, _ptr(tris), len(tris), _ptr(mat), max_depth, _ptr(rays), _ptr(hits), _ptr(paths), _ptr(samples), n,
+                                   _ptr(out_rays), _ptr(out_paths), _ptr(out_samples), C.byref(count), _ptr(frame), frame_words)
+    if rc != 0:
+        raise RaccError(rc, "racc_ptdev_test_shade failed")
+    k = int(count.value)
+    return dict(count=k, rays=out_rays[:k], paths=out_paths[:k], samples=out_samples[:k], frame=frame)
+
+
 def path_trace(scene_bin, width, height, spp_first, spp_count, device=0, max_depth=0, cpu_threads=0, shading="cpu", samples_per_batch=0):
     """Render samples [spp_first, spp_first+spp_count) of a reference-format scene file with the path-tracing consumer.
     shading="cpu": spawn/shade callbacks on host threads through racc::render (rayaccel_amd/csrc/pathtracer.cpp, the

@@ -75,6 +75,11 @@ def test_consumer_libraries_load_and_export_their_entry_points():
         lib = C.CDLL(path)
         if sym:
             assert hasattr(lib, sym)
+        # the test entries that run the consumers' arithmetic and kernels on arrays a test supplies (tests/test_pt_reference.py, tests/test_gpu_pt_kernels.py)
+        hooks = {"racc_pt_render_file": ("racc_pt_test_primary_rays", "racc_pt_test_shade"),
+                 "racc_ptdev_render_file": ("racc_ptdev_test_gen", "racc_ptdev_test_shade", "racc_ptdev_capture_round", "racc_ptdev_capture_round_paths", "racc_ptdev_compute_units")}
+        for h in hooks.get(sym, ()):
+            assert hasattr(lib, h), h
         out = os.popen("ldd %s" % path).read()
         assert "libracc_hip.so" in out and "oracle" not in out and "torch" not in out
 
