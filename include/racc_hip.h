@@ -559,6 +559,21 @@ int racc_host_world_prepare(const float* transforms12, const float* root_boxes6,
 int racc_host_scene_device_nodes(const void* nodes64, uint32_t node_count, uint32_t pair_count, uint32_t remap_count, int order,
                                  void* out64, uint32_t capacity, uint32_t* count);
 
+/* The 4-wide device records racc_hip_scene_upload builds for the wide kernels (for tools and tests; needs no GPU): the very collapse and
+ * quantisation that upload runs, with the same refusals.
+ *   format 45  the 128 B record of kernel_variant 45-49: words 0-3 the four child references (inner ones re-numbered breadth first),
+ *              words 4-27 the planes lo.x hi.x lo.y hi.y lo.z hi.z, four children each — every used box bit-equal to a box of the blob —,
+ *              word 28 the number of used slots (slots [0, used); host-side bookkeeping, no kernel reads it), words 29-31 zero.  An unused
+ *              slot holds six planes at +inf and the reference of a real leaf.
+ *   format 50  the 64 B compressed record of kernel_variant 50-53: words 0-3 the references, 4-6 the frame's origin, 7-9 its scale
+ *              (x, y, z), 10-15 one byte per child for lo.x hi.x lo.y hi.y lo.z hi.z; a plane decodes as fmaf(float(byte), scale, origin)
+ *              and the decoded box contains the blob's.  An unused slot holds lower bytes 255, upper bytes 0 and the reference of a real
+ *              leaf.  RACC_HIP_ERR_INVALID: a child box that is not finite; RACC_HIP_ERR_LIMIT: a frame whose extent overflows binary32.
+ * *stack_bound = the number of stack entries a traversal of these records can need at most (what upload sizes the spill area by).
+ * out may be NULL (then only *count and *stack_bound are returned); capacity in records. */
+int racc_host_scene_wide_nodes(const void* nodes64, uint32_t node_count, uint32_t pair_count, uint32_t remap_count, int format,
+                               void* out, uint32_t capacity, uint32_t* count, uint32_t* stack_bound);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,7 +27,7 @@ assert BVH2_NODE_DTYPE.itemsize == 48 and GPU_NODE_DTYPE.itemsize == 64 and PAIR
 def build(force=False):
     """Compile oracle/libracc_oracle.so with gcc (building the checker is not using it)."""
     src = os.path.join(_HERE, "racc_oracle.c")
-    if force or not os.path.exists(_LIB_PATH) or os.path.getmtime(_LIB_PATH) < max(os.path.getmtime(src), os.path.getmtime(os.path.join(_HERE, "racc_oracle_simd.c")), os.path.getmtime(os.path.join(_HERE, "racc_oracle_simd512.c"))):
+    if force or not os.path.exists(_LIB_PATH) or os.path.getmtime(_LIB_PATH) < max(os.path.getmtime(src), os.path.getmtime(os.path.join(_HERE, "racc_oracle_wide.c")), os.path.getmtime(os.path.join(_HERE, "racc_oracle_simd.c")), os.path.getmtime(os.path.join(_HERE, "racc_oracle_simd512.c"))):
         subprocess.check_call(["make", "-s", "-C", _HERE, "libracc_oracle.so"])
     # oracle/_ref: the reference's own traversal kernel, built only where /root/reference exists (this container)
     subprocess.call(["make", "-s", "-C", _HERE, "ref"], stdout=subprocess.DEVNULL)
@@ -64,6 +64,14 @@ def lib():
         _lib.orc_brute_one.restype = C.c_int
         _lib.orc_pt_sample_material.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp]
         _lib.orc_pt_sample_material.restype = C.c_int
+        _lib.orc_collapse_wide.argtypes = [vp, u32, vp, vp]
+        _lib.orc_collapse_wide.restype = u32
+        _lib.orc_quantise_wide.argtypes = [vp, u32, vp]
+        _lib.orc_quantise_wide.restype = C.c_int
+        _lib.orc_decode_wide.argtypes = [vp, C.c_int, u32, vp]
+        _lib.orc_decode_wide.restype = None
+        _lib.orc_traverse_wide_mt.argtypes = [vp, C.c_int, vp, vp, vp, vp, u32, u32, vp, vp, u32, C.c_int, u32, vp, vp]
+        _lib.orc_traverse_wide_mt.restype = None
     return _lib
 
 
@@ -206,6 +214,60 @@ def brute_one(vertices, indices, triangle, ray):
     t, u, vv = C.c_double(0), C.c_double(0), C.c_double(0)
     hit = lib().orc_brute_one(_p(v), _p(idx), int(triangle), _p(ray), C.byref(t), C.byref(u), C.byref(vv))
     return bool(hit), t.value, u.value, vv.value
+
+
+# ------------------------------------------------------------------------------------------------ the 4-wide model (racc_oracle_wide.c)
+WIDE_COUNTERS = ("node_visits", "pair_tests", "differ", "ties", "closer", "aliases", "others", "max_depth")
+WIDE_ORDER_PRODUCT, WIDE_ORDER_HIGHEST_AMONG_EQUALS, WIDE_ORDER_REVERSED_PUSH = 0, 1, 2
+
+
+def collapse_wide(nodes):
+    """The model's collapse of a reference-format node blob -> ([N, 32] uint32 words: the 128 B records of format 45, stack_bound)."""
+    nodes = np.ascontiguousarray(nodes)
+    assert nodes.dtype.itemsize == 64 and len(nodes)
+    out = np.zeros((len(nodes), 32), np.uint32)
+    bound = C.c_uint32(0)
+    n = lib().orc_collapse_wide(_p(nodes), len(nodes), _p(out), C.byref(bound))
+    return out[:n].copy(), bound.value
+
+
+def quantise_wide(wide):
+    """The model's quantisation of format-45 records -> (rc, [N, 16] uint32 words: the 64 B records of format 50); rc 0, -1 (a child box is
+    not finite) or -4 (a frame's extent overflows binary32) as the product's racc_host_scene_wide_nodes."""
+    wide = np.ascontiguousarray(wide, np.uint32)
+    out = np.zeros((len(wide), 16), np.uint32)
+    rc = lib().orc_quantise_wide(_p(wide), len(wide), _p(out))
+    return rc, out
+
+
+def decode_wide(records, fmt):
+    """The planes the model's traversal tests a ray against: float32 [N, 6, 4] — lo.x hi.x lo.y hi.y lo.z hi.z of the four children."""
+    records = np.ascontiguousarray(records, np.uint32)
+    assert records.shape[1] == (32 if fmt == 45 else 16)
+    out = np.zeros((len(records), 6, 4), np.float32)
+    lib().orc_decode_wide(_p(records), fmt, len(records), _p(out))
+    return out
+
+
+def traverse_wide(records, fmt, scene, rays, env=None, order=WIDE_ORDER_PRODUCT, threads=1, compare=True):
+    """The exact model of the 4-wide kernels on DEVICE RECORDS (format 45: [N, 32] words, 50: [N, 16]) with `scene`'s pairs and remap.
+    -> (RESULT_DTYPE[n], deepest stack level per ray uint32[n], counters dict: WIDE_COUNTERS; with compare the binary oracle runs next to
+    the model on scene["nodes"] and the differing records are counted by kind).  `order` is for tests only."""
+    rays = np.ascontiguousarray(rays)
+    assert rays.dtype == RAY_DTYPE and fmt in (45, 50)
+    records = np.ascontiguousarray(records, np.uint32)
+    assert records.ndim == 2 and records.shape[1] == (32 if fmt == 45 else 16)
+    n = len(rays)
+    out, depth, counters = np.zeros(n, RESULT_DTYPE), np.zeros(n, np.uint32), np.zeros(len(WIDE_COUNTERS), np.uint64)
+    envp, w, h = None, 0, 0
+    if env is not None:
+        env = np.ascontiguousarray(env, dtype=np.float32)
+        h, w = env.shape[0], env.shape[1]
+        envp = _p(env)
+    bvh2 = np.ascontiguousarray(scene["nodes"]) if compare else None
+    pairs, remap = np.ascontiguousarray(scene["pairs"]), np.ascontiguousarray(scene["remap"], dtype=np.uint32)
+    lib().orc_traverse_wide_mt(_p(records), fmt, _p(bvh2), _p(pairs), _p(remap), envp, w, h, _p(rays), _p(out), n, int(order), int(threads), _p(depth), _p(counters))
+    return out, depth, dict(zip(WIDE_COUNTERS, (int(c) for c in counters)))
 
 
 def algorithmic_bytes(results, nv, npairs):

@@ -166,6 +166,46 @@ void orc_env_sample(const float* env, uint32_t envW, uint32_t envH, const float 
                + (1.0f - a) * b * t01[c] + a * b * t11[c];
 }
 
+/* Ray admission, Kernels.h:145-160: the rays this restatement defines to miss (header note) return 0; otherwise the clamped
+ * direction (epsilon, Kernels.h:149-157) and the slab constants 1/d and -o/d (Kernels.h:159-160).  Shared by every traversal
+ * order in this library (the binary one below, the 4-wide model of racc_oracle_wide.c). */
+static inline int ray_admit(const orc_ray* in, ray_state* ray, float invDir[3], float OoD[3]) {
+    for (int k = 0; k < 3; ++k) { ray->o[k] = in->origin[k]; ray->d[k] = in->dir[k]; }
+    ray->tNear = in->minT; ray->tFar = in->maxT;
+
+    int finite = isfinite(ray->tNear) && !isnan(ray->tFar); /* maxT = +inf is a legitimate "no limit" */
+    for (int k = 0; k < 3; ++k) finite = finite && isfinite(ray->o[k]) && isfinite(ray->d[k]);
+    if (!finite)
+        return 0;
+
+    const float epsilon = 1e-10f; /* Kernels.h:149-157 */
+    for (int k = 0; k < 3; ++k)
+        if (fabsf(ray->d[k]) < epsilon) ray->d[k] = copysignf(epsilon, ray->d[k]);
+
+    for (int k = 0; k < 3; ++k) { invDir[k] = 1.0f / ray->d[k]; OoD[k] = -ray->o[k] * invDir[k]; }
+    return 1;
+}
+
+/* The result record of an admitted ray, Kernels.h:213-239. */
+static inline void ray_epilogue(const uint32_t* remap, const float* env, uint32_t envW, uint32_t envH,
+                                const ray_state* ray, const hit_state* hitp, orc_result* out) {
+    const hit_state hit = *hitp;
+    if (hit.index == -1) { /* Kernels.h:213-222 */
+        float rgb[3];
+        orc_env_sample(env, envW, envH, ray->d, rgb);
+        out->triangle = 0xFFFFFFFFu; out->t = rgb[0]; out->u = rgb[1]; out->v = rgb[2];
+    } else { /* Kernels.h:223-239 */
+        uint32_t index = remap[hit.index];
+        const uint32_t edge = index >> 30;
+        index &= 0x3FFFFFFFu;
+        const float bx = hit.u, by = hit.v, bz = 1.0f - hit.u - hit.v;
+        float u = bx, v = by;
+        if (edge == 1) { u = bz; v = bx; }       /* barys.zxy */
+        else if (edge == 2) { u = by; v = bz; }  /* barys.yzx */
+        out->triangle = index; out->t = hit.t; out->u = u; out->v = v;
+    }
+}
+
 /* Optional per-node visit histogram (analysis aid for device-layout decisions). */
 static uint32_t* g_visit_hist = 0;
 void orc_set_visit_histogram(uint32_t* hist) { g_visit_hist = hist; }
@@ -177,25 +217,14 @@ static void traverse_one(const orc_gpu_node* nodes, const orc_pair* pairs, const
                          uint32_t* nvOut, uint32_t* npOut, uint32_t* depthOut) {
     ray_state ray;
     uint32_t nv = 0, np = 0, maxDepth = 0;
-    for (int k = 0; k < 3; ++k) { ray.o[k] = in->origin[k]; ray.d[k] = in->dir[k]; }
-    ray.tNear = in->minT; ray.tFar = in->maxT;
-
-    int finite = isfinite(ray.tNear) && !isnan(ray.tFar); /* maxT = +inf is a legitimate "no limit" */
-    for (int k = 0; k < 3; ++k) finite = finite && isfinite(ray.o[k]) && isfinite(ray.d[k]);
-    if (!finite) {
+    float invDir[3], OoD[3];
+    if (!ray_admit(in, &ray, invDir, OoD)) {
         out->triangle = 0xFFFFFFFFu; out->t = out->u = out->v = 0.0f;
         if (nvOut) *nvOut = 0;
         if (npOut) *npOut = 0;
         if (depthOut) *depthOut = 0;
         return;
     }
-
-    const float epsilon = 1e-10f; /* Kernels.h:149-157 */
-    for (int k = 0; k < 3; ++k)
-        if (fabsf(ray.d[k]) < epsilon) ray.d[k] = copysignf(epsilon, ray.d[k]);
-
-    float invDir[3], OoD[3];
-    for (int k = 0; k < 3; ++k) { invDir[k] = 1.0f / ray.d[k]; OoD[k] = -ray.o[k] * invDir[k]; }
 
     hit_state hit = { -1, ray.tFar, 0.0f, 0.0f };
     uint32_t node = 0x80000000u;
@@ -232,20 +261,7 @@ static void traverse_one(const orc_gpu_node* nodes, const orc_pair* pairs, const
         node = stack[--head];
     }
 
-    if (hit.index == -1) { /* Kernels.h:213-222 */
-        float rgb[3];
-        orc_env_sample(env, envW, envH, ray.d, rgb);
-        out->triangle = 0xFFFFFFFFu; out->t = rgb[0]; out->u = rgb[1]; out->v = rgb[2];
-    } else { /* Kernels.h:223-239 */
-        uint32_t index = remap[hit.index];
-        const uint32_t edge = index >> 30;
-        index &= 0x3FFFFFFFu;
-        const float bx = hit.u, by = hit.v, bz = 1.0f - hit.u - hit.v;
-        float u = bx, v = by;
-        if (edge == 1) { u = bz; v = bx; }       /* barys.zxy */
-        else if (edge == 2) { u = by; v = bz; }  /* barys.yzx */
-        out->triangle = index; out->t = hit.t; out->u = u; out->v = v;
-    }
+    ray_epilogue(remap, env, envW, envH, &ray, &hit, out);
     if (nvOut) *nvOut = nv;
     if (npOut) *npOut = np;
     if (depthOut) *depthOut = maxDepth;

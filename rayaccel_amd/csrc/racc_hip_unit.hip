@@ -13,3 +13,4 @@
 #include <array>
 #include "racc_world.inc"
 #include "racc_world_occlusion.inc"
+#include "racc_wide_format.inc"

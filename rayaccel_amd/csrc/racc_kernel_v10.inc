@@ -20,7 +20,13 @@
 // oracle/wide_sim quant=1); a pair test is the reference's own and tFar only shrinks through real hits, so the closest hit
 // is the oracle's, bit for bit, except (a) exact-distance ties, as for V9, and (b) a hit the reference's own box test culled
 // although its pair test accepts it (box vs triangle rounding at a box face): then this kernel reports the CLOSER hit.
-// tests/helpers.py::assert_same_closest_hit allows exactly these two; neither has been observed.
+// tests/helpers.py::assert_same_closest_hit allows exactly these two.  Both are COUNTED by the exact model of this format
+// (oracle/racc_oracle_wide.c — the host's records walked by the wideStep rule below), to which every instantiation of this
+// kernel is held bit for bit (tests/test_gpu_wide_exact.py, tests/test_gpu_edge_cases.py).  On the small test scene, 22,384
+// rays (a tile of primaries + 6000 random ones), records that differ from the binary oracle: (a) ties 0, (b) closer hits 0 on
+// both trees, plus 2 aliases on the library-default tree (a triangle that spatial splits put into two leaves, met through its
+// other reference); on the 40-deep comb 0 / 0 / 0; on tests/helpers.py::tie_scene every one of the 64 records is a tie, and the
+// id reported is the one the rule below dictates (tests/test_wide_format.py).
 //
 // Structure: V8's (racc_kernel_v8.inc) — persistent waves, chained launches, quad-cooperative LDS-DMA fetch, header, leaf
 // step and fused step verbatim — with V9's wide step (nearest hit child next, the others pushed in slot order) behind a

@@ -138,6 +138,7 @@ ABI = {
     "racc_host_blobs_refit": (_i, [_vp, _u32, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _vp]),
     "racc_host_world_prepare": (_i, [_vp, _vp, _u32, _vp, _vp, _P(C.c_float), _vp, _u32, _P(_u32), _vp, _P(_u32)]),
     "racc_host_scene_device_nodes": (_i, [_vp, _u32, _u32, _u32, _i, _vp, _u32, _P(_u32)]),
+    "racc_host_scene_wide_nodes": (_i, [_vp, _u32, _u32, _u32, _i, _vp, _u32, _P(_u32), _P(_u32)]),
 }
 
 _lib = None
@@ -264,6 +265,10 @@ class HostScene:
         """The 64 B device records racc_hip_scene_upload lays the node blob out as: see device_nodes() below."""
         return device_nodes(self.nodes, len(self.pairs), len(self.remap), order)
 
+    def wide_nodes(self, format=45):
+        """The 4-wide device records racc_hip_scene_upload builds for kernel_variant 45-49 (format 45) or 50-53 (format 50): see wide_nodes() below."""
+        return wide_nodes(self.nodes, len(self.pairs), len(self.remap), format)
+
 
 def device_nodes(nodes, pair_count, remap_count, order=1):
     """The 64 B device records racc_hip_scene_upload lays a reference-format node blob out as (racc_host_scene_device_nodes; no GPU
@@ -276,6 +281,20 @@ def device_nodes(nodes, pair_count, remap_count, order=1):
     out = np.zeros((n.value, 16), np.uint32)
     _check(lib.racc_host_scene_device_nodes(*args, _ptr(out), n.value, C.byref(n)))
     return out
+
+
+def wide_nodes(nodes, pair_count, remap_count, format=45):
+    """The 4-wide device records racc_hip_scene_upload collapses a reference-format node blob into (racc_host_scene_wide_nodes; no GPU needed).
+    format 45: [N, 32] uint32 words, the 128 B record of kernel_variant 45-49; format 50: [N, 16] words, the 64 B compressed record of
+    kernel_variant 50-53 (include/racc_hip.h describes both).  Returns (records, stack_bound)."""
+    lib = load_library()
+    nodes = np.ascontiguousarray(nodes)
+    n, bound = C.c_uint32(0), C.c_uint32(0)
+    args = (_ptr(nodes), len(nodes), pair_count, remap_count, int(format))
+    _check(lib.racc_host_scene_wide_nodes(*args, None, 0, C.byref(n), C.byref(bound)))
+    out = np.zeros((n.value, 32 if int(format) == 45 else 16), np.uint32)
+    _check(lib.racc_host_scene_wide_nodes(*args, _ptr(out), n.value, C.byref(n), C.byref(bound)))
+    return out, bound.value
 
 
 def host_refit(blobs, vertices, indices):

@@ -355,3 +355,138 @@ def book_rays(sc, k=126):
     d = np.concatenate([-n, n, through - np.array([[3.0, -2.0, 0.7]]), [[0, 0, 1.0], [0, 0, 1.0]]])
     d /= np.linalg.norm(d, axis=1, keepdims=True)
     return make_rays(o, d)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the exact 4-wide model
+WIDE_FORMAT = {45: 45, 46: 45, 47: 45, 48: 45, 49: 45, 50: 50, 51: 50, 52: 50, 53: 50}      # kernel_variant -> device record format (128 B / 64 B compressed)
+
+
+def wide_model(blobs, fmt, rays, env=None, order=0):
+    """What a kernel of device format `fmt` (45 / 50) must report for `rays`, record for record: the product's own device records
+    (racc_host_scene_wide_nodes: what upload builds) traversed by the exact model (oracle/racc_oracle_wide.c).
+    -> (results, deepest stack level per ray, counters, stack_bound)."""
+    from rayaccel_amd import engine
+    records, bound = engine.wide_nodes(blobs["nodes"], len(blobs["pairs"]), len(blobs["remap"]), fmt)
+    res, depth, counters = orc.traverse_wide(records, fmt, blobs, rays, env=env, order=order, threads=4)
+    return res, depth, counters, bound
+
+
+def assert_wide_exact(got, model, what=""):
+    """A 4-wide kernel against the exact model of its device format: triangle, t, u and v bit for bit; a miss record bit for bit on the
+    triangle word, its three radiance floats within 1e-5 of the oracle's sampler (acosf: libm vs ocml, as assert_bit_exact)."""
+    assert got.dtype == model.dtype == synth.RESULT_DTYPE and len(got) == len(model)
+    bad = np.nonzero(got["triangle"] != model["triangle"])[0]
+    assert len(bad) == 0, "%s: %d records report another triangle than the model, e.g. ray %d: got %d (t=%r), model %d (t=%r)" % (
+        what, len(bad), bad[0], got["triangle"][bad[0]], got["t"][bad[0]], model["triangle"][bad[0]], model["t"][bad[0]])
+    hit = model["triangle"] != MISS
+    for f in ("t", "u", "v"):
+        bad = np.nonzero(got[f][hit].view(np.uint32) != model[f][hit].view(np.uint32))[0]
+        assert len(bad) == 0, "%s: %s differs from the model in %d hit records, e.g. got %r, model %r" % (what, f, len(bad), got[f][hit][bad[:4]], model[f][hit][bad[:4]])
+        np.testing.assert_allclose(got[f][~hit], model[f][~hit], rtol=1e-5, atol=1e-5, err_msg="%s miss colour" % what)
+
+
+def _lone_pair(p0, p1, p2):
+    """The 48-byte record of an unpaired triangle (p3 = p1, Scene.cpp:174-178)."""
+    p0, p1, p2 = (np.asarray(x, np.float32) for x in (p0, p1, p2))
+    rec = np.zeros(1, orc.PAIR_DTYPE)[0]
+    rec["e1"], rec["e2"], rec["p0"] = p0 - p1, p2 - p0, p0
+    rec["e3x"], rec["e3y"], rec["e3z"] = p1 - p0
+    return rec
+
+
+TIE_GROUPS = 16
+TIE_FAR = (4, 6)      # per group (alternating): bit s set = the leaf box of slot s starts farther along the rays
+
+
+def tie_scene():
+    """A hand-made reference-format blob in which the ORDER RULE of the 4-wide kernels decides the answer (64 triangles).
+
+    Sixteen groups side by side along x under four levels of upper nodes (which the collapse folds into two levels of wide nodes, so that
+    every group becomes ONE wide node of its own).  A group is four one-triangle leaves under a BVH2 node with two inner children: the wide
+    node holds the leaves in slots 0-3.  The four triangles of a group are exact duplicates of each other (coplanar, z = 10: the same pair
+    record under four triangle ids), so a ray that hits one hits all four at the same distance bit for bit, and the pair test — closed at
+    tFar, Kernels.h:88 — keeps the LAST one tested: the reported id says in which order the leaves were visited.  The leaf boxes of a group
+    are identical (z from 9: equal entry keys bit for bit) except those of the slots in the group's TIE_FAR mask, which start at z = 9.5.
+    With slot 2 far (mask 4):
+      the 4-wide rule (nearest first, lowest slot among equals, the others pushed in slot order)   visits 0 3 2 1 -> reports slot 1
+      highest slot among equals                                                                    visits 3 2 1 0 -> reports slot 0
+      reversed push order                                                                          visits 0 1 2 3 -> reports slot 3
+      the binary reference order (nearer child first, the first one among equals)                  visits 0 1 3 2 -> reports slot 2
+    and the same four answers with slots 1 and 2 far (mask 6).  tests/test_wide_format.py asserts, per ray, that the four answers are
+    pairwise different — computed, not taken from this table.  Triangle id = 4 * group + slot.  Returns (blobs, rays)."""
+    G = TIE_GROUPS
+    nodes = np.zeros(3 * G + (G - 1), orc.GPU_NODE_DTYPE)
+    pairs = np.zeros(4 * G, orc.PAIR_DTYPE)
+    remap = np.zeros(8 * G, np.uint32)
+    top = G - 1                                    # nodes [0, G-1): a balanced binary tree over the groups; group g's three nodes at top + 3g
+    def group_box(g0, g1):
+        return (4.0 * g0 - 1.5, -1.5, 9.0), (4.0 * (g1 - 1) + 1.5, 1.5, 11.0)
+    next_top = [1]
+    def build(idx, g0, g1):                        # subtree over groups [g0, g1) rooted at upper node idx
+        mid = (g0 + g1) // 2
+        for side, (a, b) in (("left", (g0, mid)), ("right", (mid, g1))):
+            if b - a == 1:
+                ref = 0x80000000 | (top + 3 * a)
+            else:
+                ref = 0x80000000 | next_top[0]
+                next_top[0] += 1
+                build(ref & 0x7FFFFFFF, a, b)
+            nodes[idx]["first" if side == "left" else "last"] = ref
+            nodes[idx][side + "Min"], nodes[idx][side + "Max"] = group_box(a, b)
+    nodes["kind"] = 1
+    build(0, 0, G)
+    o, d = [], []
+    for g in range(G):
+        x = 4.0 * g
+        far = TIE_FAR[g % len(TIE_FAR)]
+        tri = _lone_pair([x - 1, -1, 10], [x + 1, -1, 10], [x, 1, 10])
+        r, a, b = top + 3 * g, top + 3 * g + 1, top + 3 * g + 2
+        lo, hi = (x - 1.5, -1.5, 9.0), (x + 1.5, 1.5, 11.0)
+        nodes[r]["first"], nodes[r]["last"] = 0x80000000 | a, 0x80000000 | b
+        nodes[r]["leftMin"], nodes[r]["leftMax"], nodes[r]["rightMin"], nodes[r]["rightMax"] = lo, hi, lo, hi
+        for slot in range(4):
+            k = 4 * g + slot
+            pairs[k] = tri
+            remap[2 * k] = k
+            n, side = (a, b)[slot // 2], ("left", "right")[slot % 2]
+            nodes[n]["first" if slot % 2 == 0 else "last"] = (1 << 24) | k
+            nodes[n][side + "Min"] = (x - 1.5, -1.5, 9.5 if (far >> slot) & 1 else 9.0)
+            nodes[n][side + "Max"] = hi
+        for (px, py, dx, dy) in ((0.0, 0.0, 0.0, 0.0), (0.3, -0.4, 0.0, 0.0), (-0.2, 0.1, 0.02, -0.01), (0.1, -0.6, -0.03, 0.02)):
+            o.append([x + px - 10 * dx, py - 10 * dy, 0.0]); d.append([dx, dy, 1.0])
+    return dict(nodes=nodes, pairs=_pad_pairs(pairs, 4 * G), remap=remap, pair_count=4 * G), make_rays(o, d)
+
+
+def frame_scene(kind):
+    """Hand-made blobs of ONE inner node with two one-triangle leaves whose boxes make a degenerate quantisation frame (the boxes are
+    hand-made and need not bound the triangles; slots 2 and 3 of the wide node are unused):
+      "flat_z"     zero extent on one axis: both boxes lie in the plane z = 5
+      "point"      zero extent on all three axes: both boxes are the point (0, 0, 0) — in the compressed format the unused slots decode to
+                   that very point too, so a ray through it ENTERS them (they hold the ref of a real leaf)
+      "one_ulp"    extents of one ulp at 1.0
+      "huge"       coordinates of +-1e30
+      "overflow"   a frame whose extent overflows binary32: refused for format 50 (RACC_HIP_ERR_LIMIT)
+      "nonfinite"  a child box with an infinite plane: refused for format 50 (RACC_HIP_ERR_INVALID)
+    Triangle 0 lies in the plane x + y + z = 0, triangle 1 in x + y + z = 3, both around the diagonal.  Returns (blobs, rays)."""
+    up = lambda v: np.nextafter(np.float32(v), np.float32(np.inf))
+    boxes = {
+        "flat_z": (((-2, -2, 5), (0.5, 2, 5)), ((-0.5, -2, 5), (2, 2, 5))),
+        "point": (((0, 0, 0), (0, 0, 0)), ((0, 0, 0), (0, 0, 0))),
+        "one_ulp": (((1, 1, 1), (up(1), up(1), up(1))), ((up(1), 1, up(1)), (up(up(1)), up(1), up(up(1))))),
+        "huge": (((-1e30, -1e30, -1e30), (-0.5e30, 1e30, 1e30)), ((0.25e30, -1e30, -1e30), (1e30, 1e30, 1e30))),
+        "overflow": (((-3e38, -1, -1), (0, 1, 1)), ((0, -1, -1), (3e38, 1, 1))),
+        "nonfinite": (((-1, -1, -1), (0, 1, 1)), ((0, -1, -1), (np.inf, 1, 1))),
+    }[kind]
+    nodes = np.zeros(1, orc.GPU_NODE_DTYPE)
+    nodes[0]["kind"], nodes[0]["first"], nodes[0]["last"] = 1, (1 << 24) | 0, (1 << 24) | 1
+    (nodes[0]["leftMin"], nodes[0]["leftMax"]), (nodes[0]["rightMin"], nodes[0]["rightMax"]) = boxes
+    pairs = np.zeros(2, orc.PAIR_DTYPE)
+    pairs[0] = _lone_pair([4, -2, -2], [-2, 4, -2], [-2, -2, 4])
+    pairs[1] = _lone_pair([5, -1, -1], [-1, 5, -1], [-1, -1, 5])
+    remap = np.array([0, 0, 1, 0], np.uint32)
+    o = [[-5, -5, -5], [-5, -5, -5], [-4, -4, -4], [6, 6, 6], [0.5, 0.25, -3], [-1, -1, 2], [1, 1, -9], [-7, -7, -7]]
+    d = [[1, 1, 1], [1, 1, 1.0001], [1.25, 1.25, 1.25], [-1, -1, -1], [0, 0, 1], [0.3, 0.3, 1], [0, 0, 1], [2, 2, 2]]
+    rays = make_rays(o, d)
+    rays["maxT"][1::2] = np.inf                 # (the boxes at 1e30 are entered only by rays without a limit)
+    grid = make_rays([[x, y, -4.0] for x in (-1.5, -0.25, 0.0, 1.0, 1.75) for y in (-1.0, 0.0, 0.5, 1.0)], [[0.01, -0.02, 1.0]] * 20)
+    return dict(nodes=nodes, pairs=_pad_pairs(pairs, 2), remap=remap, pair_count=2), np.concatenate([rays, grid])

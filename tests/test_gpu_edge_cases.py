@@ -13,7 +13,8 @@ allows 127, Scene.cpp:294-312).  Here every case is uploaded through racc_hip_sc
   * the reference's own OpenCL kernel on the same blobs (oracle/_ref, where built).
 
 Bar: the V8 family bit-exact against the oracle (primId, t, u, v; miss colours 1e-5); the wide kernels the oracle's closest hit
-except exact-distance ties (tests/helpers.py::assert_same_closest_hit); the reference kernel north_star's 1e-4.  The scene info's
+except exact-distance ties (tests/helpers.py::assert_same_closest_hit) AND bit-exact against the exact model of their device format
+(oracle/racc_oracle_wide.c, tests/helpers.py::assert_wide_exact); the reference kernel north_star's 1e-4.  The scene info's
 max_leaf_pairs is asserted, so every test says what it exercised."""
 import numpy as np
 import pytest
@@ -21,8 +22,8 @@ import pytest
 import rayaccel_amd as ra
 from oracle import oracle as orc, ref_kernel
 from rayaccel_amd import synth
-from helpers import (MISS, QUANT_VARIANTS, WIDE_VARIANTS, assert_bit_exact, assert_matches_arbiter, assert_same_closest_hit,
-                     book_rays, book_scene, compare_with_reference_kernel, far_scene, leaf_rays, leaf_scene, make_rays, sliver_scene)
+from helpers import (MISS, QUANT_VARIANTS, WIDE_FORMAT, WIDE_VARIANTS, assert_bit_exact, assert_matches_arbiter, assert_same_closest_hit, assert_wide_exact,
+                     book_rays, book_scene, compare_with_reference_kernel, far_scene, leaf_rays, leaf_scene, make_rays, sliver_scene, wide_model)
 
 pytestmark = pytest.mark.gpu
 
@@ -83,6 +84,7 @@ def run_everywhere(contexts, blobs, rays, what, env=ENV, min_leaf=None, arbiter=
     """Uploads `blobs` into every context, traces `rays` through the host path and the device path, holds every result to the oracle —
     and the reference's own kernel on the same blobs to it as well.  Returns the oracle's records."""
     ref = orc.traverse(blobs, rays, env=env)
+    model = {fmt: wide_model(blobs, fmt, rays, env=env)[0] for fmt in (45, 50)}      # what a 4-wide kernel must report, record for record
     for name, ctx in contexts.items():
         variant = CONFIGS[name].get("kernel_variant", 0)
         scene = ctx.upload_scene(blobs["nodes"], blobs["pairs"], blobs["remap"])
@@ -95,6 +97,7 @@ def run_everywhere(contexts, blobs, rays, what, env=ENV, min_leaf=None, arbiter=
             if variant in WIDE_VARIANTS:
                 arb = dict(arbiter, rays=rays) if (arbiter is not None and variant in QUANT_VARIANTS) else None
                 assert_same_closest_hit(got, ref, label, max_ties=len(rays) if max_ties is None else max_ties, arbiter=arb)
+                assert_wide_exact(got, model[WIDE_FORMAT[variant]], label + " | exact model")
             else:
                 assert_bit_exact(got, ref, label)
         scene.destroy()

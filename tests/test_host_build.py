@@ -237,7 +237,7 @@ def test_device_node_order_is_the_same_tree(small_scene, small_host, order):
         used[idx] = True
     assert used.sum() == n and not dev[~used].any()               # the rest is all-zero padding
     assert len(dev) - n <= max(2, n // 50)
-    rays = np.concatenate([synth.primary_rays(small_scene["camera"], 96, 96)[0], synth.random_rays(6000, seed=3, ymax=30.0)])
+    rays = np.concatenate([synth.primary_rays(small_scene["camera"], 128, 128)[0], synth.random_rays(6000, seed=3, ymax=30.0)])
     a = orc.traverse(small_host.blobs(), rays, env=small_scene["env"])
     b = orc.traverse(dict(small_host.blobs(), nodes=_device_to_reference(dev)), rays, env=small_scene["env"])
     assert a.tobytes() == b.tobytes()
@@ -292,7 +292,7 @@ def test_device_node_order_with_a_cached_top_is_the_same_tree(small_scene, small
         parent[idx] = rows
     assert used.sum() == n and not dev[~used].any()
     assert len(dev) - n <= max(3, n // 50)
-    rays = np.concatenate([synth.primary_rays(small_scene["camera"], 96, 96)[0], synth.random_rays(6000, seed=3, ymax=30.0)])
+    rays = np.concatenate([synth.primary_rays(small_scene["camera"], 128, 128)[0], synth.random_rays(6000, seed=3, ymax=30.0)])
     a = orc.traverse(small_host.blobs(), rays, env=small_scene["env"])
     b = orc.traverse(dict(small_host.blobs(), nodes=_device_to_reference(dev)), rays, env=small_scene["env"])
     assert a.tobytes() == b.tobytes()
