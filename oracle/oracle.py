@@ -11,7 +11,7 @@ import subprocess
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-_LIB_PATH = os.path.join(_HERE, "libracc_oracle.so")
+_LIB_PATH = os.environ.get("RACC_ORACLE_LIB") or os.path.join(_HERE, "libracc_oracle.so")      # RACC_ORACLE_LIB: a build of a COPY of these sources (tools/oracle_fault_injection.py)
 
 RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("minT", "<f4"), ("dir", "<f4", 3), ("maxT", "<f4")], align=False)
 RESULT_DTYPE = np.dtype([("triangle", "<u4"), ("t", "<f4"), ("u", "<f4"), ("v", "<f4")], align=False)

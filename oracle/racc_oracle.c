@@ -16,8 +16,10 @@
  *   mad_cross(a,b).x    = fmaf(a.y,b.z, -(a.z*b.y))      (Kernels.h:23-25)
  *   native_recip(x)     = 1.0f/x  (correctly rounded)     (Kernels.h:107)
  *   native_rsqrt(x)     = 1.0f/sqrtf(x)                   (Kernels.h:216)
- *   fmin/fmax           = (a<b?a:b)/(a>b?a:b); equal to IEEE minNum/maxNum for
- *                         the finite, zero-sign-insensitive uses below
+ *   fmin/fmax           = IEEE minNum/maxNum (a NaN operand is ignored), the select
+ *                         (a<b?a:b)/(a>b?a:b) among ordered operands; from finite
+ *                         scenes a NaN reaches them only as a NaN tFar, the first
+ *                         operand, where both agree
  *   signbit(tLast-tFirst) is evaluated as (tLast < tFirst) so that the sign of
  *   a zero produced by min/max can never steer the traversal (Kernels.h:193).
  * Rays with a non-finite origin/direction/minT component or a NaN maxT are
@@ -40,17 +42,37 @@ typedef union { float f; uint32_t u; int32_t i; } fbits;
 
 static inline uint32_t f2u(float f) { fbits b; b.f = f; return b.u; }
 static inline float u2f(uint32_t u) { fbits b; b.u = u; return b.f; }
-static inline float omin(float a, float b) { return a < b ? a : b; }
-static inline float omax(float a, float b) { return a > b ? a : b; }
+/* tests/test_float_range.py compiles this file with -DORC_COUNT_NAN to learn whether a NaN reaches omin / omax as the FIRST operand
+ * (counter 0: the select a < b ? a : b and minNum agree there), as the SECOND (counter 1: there they differ) or an operand of the pair
+ * test's sign tests and comparisons (counter 2) from finite input.  The counters change no result. */
+#ifdef ORC_COUNT_NAN
+static uint64_t g_nan_count[3] = { 0, 0, 0 };
+void orc_nan_counts(uint64_t out[3], int reset) {
+    for (int k = 0; k < 3; ++k) {
+        out[k] = __atomic_load_n(&g_nan_count[k], __ATOMIC_RELAXED);
+        if (reset) __atomic_store_n(&g_nan_count[k], 0, __ATOMIC_RELAXED);
+    }
+}
+#define ORC_NOTE_NAN(which, cond) do { if (cond) __atomic_fetch_add(&g_nan_count[which], 1, __ATOMIC_RELAXED); } while (0)
+#else
+#define ORC_NOTE_NAN(which, cond) ((void)0)
+#endif
+/* IEEE minNum / maxNum: a NaN operand is ignored (both NaN: NaN), as OpenCL's fmin / fmax and the GPU's v_min_f32 / v_max_f32 do.  Among
+ * ordered operands it is the select a < b ? a : b, which on equality (zeros of either sign included) returns the second operand. */
+static inline float omin(float a, float b) { ORC_NOTE_NAN(0, a != a); ORC_NOTE_NAN(1, b != b); return (a < b || b != b) ? a : b; }
+static inline float omax(float a, float b) { ORC_NOTE_NAN(0, a != a); ORC_NOTE_NAN(1, b != b); return (a > b || b != b) ? a : b; }
 
 static inline float dot3(const float a[3], const float b[3]) {
     return fmaf(a[2], b[2], fmaf(a[1], b[1], a[0] * b[0]));
 }
 /* Kernels.h:23-25 */
+/* The negation is a flip of the sign BIT, of a NaN too: written as -(x) the compiler folds it into a fused multiply-subtract, which
+ * leaves a NaN product's sign alone — and the pair test reads sign bits ((int)(iU | iV) < 0).  The SIMD ports and the GPU kernels flip. */
+static inline float oneg(float x) { return u2f(f2u(x) ^ 0x80000000u); }
 static inline void mad_cross(float r[3], const float a[3], const float b[3]) {
-    r[0] = fmaf(a[1], b[2], -(a[2] * b[1]));
-    r[1] = fmaf(a[2], b[0], -(a[0] * b[2]));
-    r[2] = fmaf(a[0], b[1], -(a[1] * b[0]));
+    r[0] = fmaf(a[1], b[2], oneg(a[2] * b[1]));
+    r[1] = fmaf(a[2], b[0], oneg(a[0] * b[2]));
+    r[2] = fmaf(a[0], b[1], oneg(a[1] * b[0]));
 }
 
 typedef struct {
@@ -82,9 +104,10 @@ static inline float pair_intersect(const orc_pair* pairs, int32_t index, const r
 
     const uint32_t iU1 = f2u(dot3(R, e2)) ^ sgnDet1;
     const uint32_t iV1 = f2u(dot3(R, e1)) ^ sgnDet1;
-    const uint32_t iU2 = f2u(-dot3(R, e1)) ^ sgnDet2;
-    const uint32_t iV2 = f2u(-dot3(R, e3)) ^ sgnDet2;
+    const uint32_t iU2 = f2u(oneg(dot3(R, e1))) ^ sgnDet2;
+    const uint32_t iV2 = f2u(oneg(dot3(R, e3))) ^ sgnDet2;
 
+    ORC_NOTE_NAN(2, det1 != det1 || det2 != det2 || tMax != tMax || u2f(iU1) != u2f(iU1) || u2f(iV1) != u2f(iV1) || u2f(iU2) != u2f(iU2) || u2f(iV2) != u2f(iV2));
     if ((int32_t)((iU1 | iV1) & (iU2 | iV2)) < 0)
         return tMax;
 
@@ -100,6 +123,7 @@ static inline float pair_intersect(const orc_pair* pairs, int32_t index, const r
     float T1 = u2f(f2u(dot3(n1, C)) ^ sgnDet1);
     const float T2 = u2f(f2u(dot3(n2, C)) ^ sgnDet2);
 
+    ORC_NOTE_NAN(2, T1 != T1 || T2 != T2);
     /* open at tNear, closed at tMax (Kernels.h:88-89) */
     outside1 = outside1 || (W1 < 0.0f || T1 <= absDet1 * tNear || T1 > absDet1 * tMax);
     outside2 = outside2 || (W2 < 0.0f || T2 <= absDet2 * tNear || T2 > absDet2 * tMax);

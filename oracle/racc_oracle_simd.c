@@ -9,7 +9,7 @@
  * lanes of a ymm register — every lane has its own node, its own stack and its own tFar and does, instruction for instruction, what
  * traverse_one() does for its ray:
  *   fmaf -> vfmadd (one rounding), a*b -> vmulps, -(a*b) -> vmulps + sign flip (never vfnmadd: that would round once instead of twice),
- *   omin/omax (a<b?a:b / a>b?a:b) -> vminps/vmaxps (same operand order: the second operand comes back on NaN or equality),
+ *   omin/omax (minNum/maxNum) -> vminps/vmaxps (same operand order: the second operand comes back on equality) + a blend where b is a NaN,
  *   1.0f/x -> vdivps (correctly rounded), comparisons ordered/unordered exactly as C's <, <=, >, != are.
  * Results are therefore BIT-IDENTICAL to orc_traverse for every ray (miss colours included: the epilogue is the scalar one).
  * Scheduling is the GPU kernel's in miniature: lanes that finish are refilled from the slice at once; one iteration runs an inner step
@@ -69,6 +69,10 @@ static inline void transpose8x4(const __m128 in[8], __m256 out[4]) {
 
 static inline __m256 neg(__m256 x) { return _mm256_xor_ps(x, _mm256_castsi256_ps(_mm256_set1_epi32((int)0x80000000u))); }
 static inline __m256 vabs(__m256 x) { return _mm256_and_ps(x, _mm256_castsi256_ps(_mm256_set1_epi32(0x7FFFFFFF))); }
+/* omin / omax: minNum / maxNum.  vminps / vmaxps return the SECOND operand on NaN or equality, which is omin / omax except where b is a NaN:
+ * there a comes back. */
+static inline __m256 vmin(__m256 a, __m256 b) { return _mm256_blendv_ps(_mm256_min_ps(a, b), a, _mm256_cmp_ps(b, b, _CMP_UNORD_Q)); }
+static inline __m256 vmax(__m256 a, __m256 b) { return _mm256_blendv_ps(_mm256_max_ps(a, b), a, _mm256_cmp_ps(b, b, _CMP_UNORD_Q)); }
 /* dot3(a, b) = fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x)) */
 static inline __m256 dot3v(__m256 ax, __m256 ay, __m256 az, __m256 bx, __m256 by, __m256 bz) {
     return _mm256_fmadd_ps(az, bz, _mm256_fmadd_ps(ay, by, _mm256_mul_ps(ax, bx)));
@@ -87,11 +91,11 @@ static inline __m256 slab(__m256 mnx, __m256 mny, __m256 mnz, __m256 mxx, __m256
     const __m256 ax = _mm256_fmadd_ps(mnx, ix, ex), bx = _mm256_fmadd_ps(mxx, ix, ex);
     const __m256 ay = _mm256_fmadd_ps(mny, iy, ey), by = _mm256_fmadd_ps(mxy, iy, ey);
     const __m256 az = _mm256_fmadd_ps(mnz, iz, ez), bz = _mm256_fmadd_ps(mxz, iz, ez);
-    const __m256 nx = _mm256_min_ps(ax, bx), fx = _mm256_max_ps(ax, bx);
-    const __m256 ny = _mm256_min_ps(ay, by), fy = _mm256_max_ps(ay, by);
-    const __m256 nz = _mm256_min_ps(az, bz), fz = _mm256_max_ps(az, bz);
-    const __m256 t0 = _mm256_max_ps(_mm256_max_ps(tNear, nx), _mm256_max_ps(ny, nz));
-    const __m256 t1 = _mm256_min_ps(_mm256_min_ps(tFar, fx), _mm256_min_ps(fy, fz));
+    const __m256 nx = vmin(ax, bx), fx = vmax(ax, bx);
+    const __m256 ny = vmin(ay, by), fy = vmax(ay, by);
+    const __m256 nz = vmin(az, bz), fz = vmax(az, bz);
+    const __m256 t0 = vmax(vmax(tNear, nx), vmax(ny, nz));
+    const __m256 t1 = vmin(vmin(tFar, fx), vmin(fy, fz));
     return _mm256_blendv_ps(t0, tFar, _mm256_cmp_ps(t0, t1, _CMP_GT_OQ));      /* if (t0 > t1) return tFar */
 }
 
@@ -184,7 +188,7 @@ static inline __attribute__((always_inline)) int simd_step(lanes_t* Lp, int* idl
             const __m256 firstDiff = _mm256_sub_ps(tFar, tFirst), lastDiff = _mm256_sub_ps(tFar, tLast);
             const __m256i any = _mm256_and_si256(innerV, _mm256_castps_si256(_mm256_cmp_ps(_mm256_add_ps(firstDiff, lastDiff), _mm256_setzero_ps(), _CMP_NEQ_UQ)));      /* Kernels.h:192 */
             const __m256 sgn = _mm256_cmp_ps(tLast, tFirst, _CMP_LT_OQ);                                                 /* signbit(tLast - tFirst), :193 */
-            const __m256i both = _mm256_and_si256(any, _mm256_castps_si256(_mm256_cmp_ps(_mm256_max_ps(tFirst, tLast), tFar, _CMP_NEQ_UQ)));      /* fmax(tFirst, tLast) != tRay, :194 */
+            const __m256i both = _mm256_and_si256(any, _mm256_castps_si256(_mm256_cmp_ps(vmax(tFirst, tLast), tFar, _CMP_NEQ_UQ)));      /* fmax(tFirst, tLast) != tRay, :194 */
             const __m256 nearKid = _mm256_blendv_ps(A[2], A[3], sgn), farKid = _mm256_blendv_ps(A[3], A[2], sgn);
             /* push the far child where both are hit: written above every lane's top unconditionally, counted by the head (stack[64] in the reference; 256 here, clamped like the scalar port) */
             uint32_t fk[LANES], hd[LANES];

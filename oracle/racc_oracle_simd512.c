@@ -3,7 +3,7 @@
  * (the GPU boxes' EPYC 9575F does).  TEST INFRASTRUCTURE ONLY (bench.py's cpu_baseline leg; tests/test_oracle.py: bit-identical to the scalar port).
  *
  * Same construction as the 8-wide file — every lane has its own node, stack and tFar and does, instruction for instruction, what traverse_one()
- * of racc_oracle.c does for its ray (vfmadd for fmaf, vmulps + sign flip for -(a*b), vminps/vmaxps in the scalar operand order, vdivps, C's
+ * of racc_oracle.c does for its ray (vfmadd for fmaf, vmulps + sign flip for -(a*b), vminps/vmaxps in the scalar operand order with a NaN second operand masked out (minNum/maxNum), vdivps, C's
  * ordered / unordered comparisons as mask compares) — with what AVX-512 adds: a 64-byte node record IS one zmm row, so sixteen nodes are sixteen
  * loads and one 16 x 16 register transpose; decisions are mask registers instead of blend vectors.  The reference's own CPU leg is 8-wide
  * (Scene.cpp:386-428, isa=avx2); this is what the same algorithm does on the cores the GPU box actually has.
@@ -61,6 +61,9 @@ static inline __attribute__((always_inline)) void transpose16(__m512 r[16]) {
 static inline __m512 neg(__m512 x) { return _mm512_castsi512_ps(_mm512_xor_si512(_mm512_castps_si512(x), _mm512_set1_epi32((int)0x80000000u))); }
 static inline __m512 vabs(__m512 x) { return _mm512_castsi512_ps(_mm512_and_si512(_mm512_castps_si512(x), _mm512_set1_epi32(0x7FFFFFFF))); }
 static inline __m512 vxor(__m512 a, __m512 b) { return _mm512_castsi512_ps(_mm512_xor_si512(_mm512_castps_si512(a), _mm512_castps_si512(b))); }
+/* omin / omax: minNum / maxNum.  vminps / vmaxps return the SECOND operand on NaN or equality; where b is a NaN, a comes back instead. */
+static inline __m512 vmin16(__m512 a, __m512 b) { return _mm512_mask_mov_ps(_mm512_min_ps(a, b), _mm512_cmp_ps_mask(b, b, _CMP_UNORD_Q), a); }
+static inline __m512 vmax16(__m512 a, __m512 b) { return _mm512_mask_mov_ps(_mm512_max_ps(a, b), _mm512_cmp_ps_mask(b, b, _CMP_UNORD_Q), a); }
 static inline __m512 dot3v(__m512 ax, __m512 ay, __m512 az, __m512 bx, __m512 by, __m512 bz) {
     return _mm512_fmadd_ps(az, bz, _mm512_fmadd_ps(ay, by, _mm512_mul_ps(ax, bx)));
 }
@@ -77,11 +80,11 @@ static inline __m512 slab(__m512 mnx, __m512 mny, __m512 mnz, __m512 mxx, __m512
     const __m512 ax = _mm512_fmadd_ps(mnx, ix, ex), bx = _mm512_fmadd_ps(mxx, ix, ex);
     const __m512 ay = _mm512_fmadd_ps(mny, iy, ey), by = _mm512_fmadd_ps(mxy, iy, ey);
     const __m512 az = _mm512_fmadd_ps(mnz, iz, ez), bz = _mm512_fmadd_ps(mxz, iz, ez);
-    const __m512 nx = _mm512_min_ps(ax, bx), fx = _mm512_max_ps(ax, bx);
-    const __m512 ny = _mm512_min_ps(ay, by), fy = _mm512_max_ps(ay, by);
-    const __m512 nz = _mm512_min_ps(az, bz), fz = _mm512_max_ps(az, bz);
-    const __m512 t0 = _mm512_max_ps(_mm512_max_ps(tNear, nx), _mm512_max_ps(ny, nz));
-    const __m512 t1 = _mm512_min_ps(_mm512_min_ps(tFar, fx), _mm512_min_ps(fy, fz));
+    const __m512 nx = vmin16(ax, bx), fx = vmax16(ax, bx);
+    const __m512 ny = vmin16(ay, by), fy = vmax16(ay, by);
+    const __m512 nz = vmin16(az, bz), fz = vmax16(az, bz);
+    const __m512 t0 = vmax16(vmax16(tNear, nx), vmax16(ny, nz));
+    const __m512 t1 = vmin16(vmin16(tFar, fx), vmin16(fy, fz));
     return _mm512_mask_blend_ps(_mm512_cmp_ps_mask(t0, t1, _CMP_GT_OQ), t0, tFar);      /* if (t0 > t1) return tFar */
 }
 
@@ -165,7 +168,7 @@ static inline __attribute__((always_inline)) int simd_step(lanes16_t* Lp, unsign
         const __m512 firstDiff = _mm512_sub_ps(tFar, tFirst), lastDiff = _mm512_sub_ps(tFar, tLast);
         const __mmask16 any = innerM & _mm512_cmp_ps_mask(_mm512_add_ps(firstDiff, lastDiff), _mm512_setzero_ps(), _CMP_NEQ_UQ);      /* Kernels.h:192 */
         const __mmask16 sgn = _mm512_cmp_ps_mask(tLast, tFirst, _CMP_LT_OQ);                                                        /* :193 */
-        const __mmask16 both = any & _mm512_cmp_ps_mask(_mm512_max_ps(tFirst, tLast), tFar, _CMP_NEQ_UQ);                            /* :194 */
+        const __mmask16 both = any & _mm512_cmp_ps_mask(vmax16(tFirst, tLast), tFar, _CMP_NEQ_UQ);                            /* :194 */
         const __m512i first = _mm512_castps_si512(N[2]), last = _mm512_castps_si512(N[3]);
         const __m512i nearKid = _mm512_mask_blend_epi32(sgn, first, last), farKid = _mm512_mask_blend_epi32(sgn, last, first);
         uint32_t fk[LANES], hd[LANES];

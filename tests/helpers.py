@@ -490,3 +490,70 @@ def frame_scene(kind):
     rays["maxT"][1::2] = np.inf                 # (the boxes at 1e30 are entered only by rays without a limit)
     grid = make_rays([[x, y, -4.0] for x in (-1.5, -0.25, 0.0, 1.0, 1.75) for y in (-1.0, 0.0, 0.5, 1.0)], [[0.01, -0.02, 1.0]] * 20)
     return dict(nodes=nodes, pairs=_pad_pairs(pairs, 2), remap=remap, pair_count=2), np.concatenate([rays, grid])
+
+
+# ---------------------------------------------------------------------------------------------------------------- the whole float range
+# Multiplying every length of a scene and of its rays by 2^k is exact in binary floating point while nothing leaves the normal range: a
+# traversal must then report the same triangle, the same u and v, and exactly 2^k t.  tests/float_range_cases.py holds the scenes.
+NODE_FLOAT_FIELDS = ("leftMin", "leftMax", "rightMin", "rightMax")
+PAIR_FLOAT_FIELDS = ("e1", "e3x", "e2", "e3y", "p0", "e3z")
+
+
+def scale_blobs(blobs, k):
+    """`blobs` with every float field of the node and pair records multiplied by 2^k (np.ldexp: exact unless the result is subnormal or
+    overflows); refs, remap and `kind` untouched."""
+    nodes, pairs = blobs["nodes"].copy(), blobs["pairs"].copy()
+    with np.errstate(all="ignore"):
+        for f in NODE_FLOAT_FIELDS:
+            nodes[f] = np.ldexp(nodes[f], k)
+        for f in PAIR_FLOAT_FIELDS:
+            pairs[f] = np.ldexp(pairs[f], k)
+    return dict(nodes=nodes, pairs=pairs, remap=blobs["remap"].copy(), pair_count=blobs["pair_count"])
+
+
+def scale_geometry(geo, k):
+    """dict(vertices, indices) with x, y, z of every vertex multiplied by 2^k (w untouched)."""
+    v = np.array(geo["vertices"], np.float32, copy=True)
+    with np.errstate(all="ignore"):
+        v[:, :3] = np.ldexp(v[:, :3], k)
+    return dict(geo, vertices=v)
+
+
+def scale_rays(rays, k):
+    """Origin, minT and maxT multiplied by 2^k; the direction untouched (t is a length, the direction a ratio)."""
+    out = rays.copy()
+    with np.errstate(all="ignore"):
+        for f in ("origin", "minT", "maxT"):
+            out[f] = np.ldexp(rays[f], k)
+    return out
+
+
+def scaled_results(res, k):
+    """What a traversal of the scaled scene must report where scaling is exact: t of the hits multiplied by 2^k; id, u, v and the miss
+    colours untouched."""
+    out = res.copy()
+    hit = res["triangle"] != MISS
+    with np.errstate(all="ignore"):
+        out["t"][hit] = np.ldexp(res["t"][hit], k)
+    return out
+
+
+def assert_same_bits_nan_aware(got, ref, what=""):
+    """assert_bit_exact, except that a float field of a hit record which is NaN in the ORACLE's record (`ref`) only has to be NaN in the
+    kernel's: the payload and the sign of a NaN are not part of the contract (x86 makes 0xFFC00000 of inf - inf, the GPU 0x7FC00000).
+    Returns the number of such fields."""
+    assert got.dtype == ref.dtype == synth.RESULT_DTYPE and len(got) == len(ref)
+    bad = np.nonzero(got["triangle"] != ref["triangle"])[0]
+    assert len(bad) == 0, "%s primId mismatch at %s: got %s want %s" % (what, bad[:8], got["triangle"][bad[:8]], ref["triangle"][bad[:8]])
+    hit = ref["triangle"] != MISS
+    excused = 0
+    for f in ("t", "u", "v"):
+        nan = hit & np.isnan(ref[f])
+        excused += int(nan.sum())
+        stray = np.nonzero(nan & ~np.isnan(got[f]))[0]
+        assert len(stray) == 0, "%s %s: the oracle's record holds a NaN, the kernel's %r (rays %s)" % (what, f, got[f][stray[:4]], stray[:8])
+        sel = hit & ~nan
+        bad = np.nonzero(got[f][sel].view(np.uint32) != ref[f][sel].view(np.uint32))[0]
+        assert len(bad) == 0, "%s %s not bit-exact at %d hits (rays %s), e.g. got %r want %r" % (what, f, len(bad), np.nonzero(sel)[0][bad[:8]], got[f][sel][bad[:4]], ref[f][sel][bad[:4]])
+        np.testing.assert_allclose(got[f][~hit], ref[f][~hit], rtol=1e-5, atol=1e-5, err_msg="%s miss colour" % what)
+    return excused

@@ -1,5 +1,8 @@
 """Shared by the instancing tests (tests/test_world_host.py, tests/test_gpu_world.py): transforms, the specification's ray transform in
 numpy.float32 and the composed expectation — orc.traverse per distinct (instance, scene), smallest t, then lowest instance index."""
+import ctypes as C
+import ctypes.util
+
 import numpy as np
 
 from oracle import oracle as orc
@@ -97,3 +100,47 @@ def assert_world_exact(got, got_inst, want, want_inst, what=""):
         assert len(bad) == 0, "%s: %s not bit-exact at %d rays, e.g. %s: got %r want %r" % (what, f, len(bad), bad[:8], got[f][bad[:8]], want[f][bad[:8]])
     miss = want["triangle"] == MISS
     assert (want_inst[miss] == NO_INSTANCE).all() and (want["t"][miss] == 0).all()
+
+
+_fmaf = None
+
+
+def _fmaf_elementwise():
+    """libm's fmaf as a numpy ufunc (numpy has no fused multiply-add), loaded on first use."""
+    global _fmaf
+    if _fmaf is None:
+        libm = C.CDLL(ctypes.util.find_library("m") or "libm.so.6")
+        libm.fmaf.argtypes, libm.fmaf.restype = [C.c_float, C.c_float, C.c_float], C.c_float
+        _fmaf = np.frompyfunc(lambda a, b, c: libm.fmaf(float(a), float(b), float(c)), 3, 1)
+    return _fmaf
+
+
+def top_level_enters(prep, rays):
+    """The top-level rule of the world kernels for a ONE-instance world, in binary32 (racc_world.inc: setWorldRay, worldWidenedEnd,
+    worldTopInnerStep over slabPair): does the ray enter the instance's padded world box in [minT, maxT widened by 2^-20 of itself]?
+    `prep` = host_world_prepare's output.  The world box is padded by ray_pad (|ox| + |oy| + |oz|) on every side; 1 / d is that of the
+    clamped direction; min / max ignore a NaN; the interval's end doubles as "missed" (so an entry distance equal to it — +inf under
+    maxT = +inf — reads as missed).  While nothing overflows the box is conservative and every ray that can hit the instance enters it
+    (world_build.cpp); this function is for the ends of the float range, where the products overflow.  It is a MODEL OF THE KERNEL's
+    rule, not an independent reference: what makes it usable is that inside the domain it is asserted to remove no hit
+    (tests/test_float_range.py), so there the expectation is the plain composition.  -> bool [N]."""
+    nodes = prep["nodes"]
+    assert len(nodes) == 1 and nodes["first"][0] == (1 << 24) and nodes["last"][0] == 0, "a one-instance world: one top-level node, the instance on the left, nothing on the right"
+    f = np.float32
+    with np.errstate(all="ignore"):
+        o, d = rays["origin"].astype(f), rays["dir"].astype(f).copy()
+        small = np.abs(d) < f(1e-10)
+        d[small] = np.copysign(f(1e-10), d[small])
+        inv = f(1.0) / d
+        e = -o * inv
+        pad = f(prep["ray_pad"]) * ((np.abs(o[:, 0]) + np.abs(o[:, 1])) + np.abs(o[:, 2]))
+        t = rays["maxT"].astype(f)
+        end = t + np.fmax(np.abs(t) * f(9.5367431640625e-07), f(1e-30))
+        lo = nodes["leftMin"][0][None, :] - pad[:, None]
+        hi = nodes["leftMax"][0][None, :] + pad[:, None]
+        fmaf = _fmaf_elementwise()
+        a, b = fmaf(lo, inv, e).astype(f), fmaf(hi, inv, e).astype(f)
+        near = np.fmax(np.fmax(rays["minT"].astype(f), np.fmin(a[:, 0], b[:, 0])), np.fmax(np.fmin(a[:, 1], b[:, 1]), np.fmin(a[:, 2], b[:, 2])))
+        far = np.fmin(np.fmin(end, np.fmax(a[:, 0], b[:, 0])), np.fmin(np.fmax(a[:, 1], b[:, 1]), np.fmax(a[:, 2], b[:, 2])))
+        entry = np.where(near > far, end, near)
+        return entry != end
