@@ -310,8 +310,9 @@ int racc_hip_refit_download(racc_hip_ctx*, racc_hip_refit*, void* nodes64_out, u
  * ≙ nothing in the reference (one flattened scene per racc::Scene, Scene.cpp:216-349); Embree's RTC_GEOMETRY_TYPE_INSTANCE and the
  * top-level / bottom-level structures of every GPU ray-tracing API are the usual counterparts.  Uploaded scenes are the bottom level; a
  * WORLD is an ordered list of `count` instances, each a 3x4 row-major object-to-world transform (twelve floats, rows of {a0 a1 a2 b}) and a
- * racc_hip_scene of the same context; several instances may name one scene.  Rigid motion costs racc_hip_world_update (no rebuild, the
- * bottom-level tree keeps its quality); a thousand copies of a mesh cost one scene plus 148 bytes each.
+ * racc_hip_scene of the same context; several instances may name one scene.  Rigid motion costs racc_hip_world_refit_device (below: the
+ * top level refitted on the device) or racc_hip_world_update (the top level rebuilt on the host) — no rebuild of a scene, the
+ * bottom-level tree keeps its quality; a thousand copies of a mesh cost one scene plus 148 bytes each.
  *
  * Semantics.  inv = the inverse transform evaluated in double precision, every coefficient rounded to float once (racc_host_world_prepare
  * returns it).  Instance i sees the ray o' = inv (o, 1), d' = inv (d, 0), each component the plain float expression
@@ -377,6 +378,51 @@ int racc_hip_world_intersect_device(racc_hip_ctx*, const racc_hip_world*, const 
 int racc_hip_world_intersect(racc_hip_ctx*, const racc_hip_world*, const void* rays, void* results, uint32_t* instances, uint32_t count);
 int racc_hip_world_occluded_device(racc_hip_ctx*, const racc_hip_world*, const void* d_rays, uint8_t* d_occluded, uint32_t count, void* stream);
 int racc_hip_world_occluded(racc_hip_ctx*, const racc_hip_world*, const void* rays, uint8_t* occluded, uint32_t count);
+
+/* ---- instancing: refit of a world's top level to moved instances, on the device ----
+ * ≙ nothing in the reference; Embree's rtcCommitScene on a scene of moved instances and every GPU API's top-level update are the usual
+ * counterparts.  What racc_hip_scene_refit* is for a scene: asynchronous, device-resident, for transforms a kernel of the caller's
+ * produces (a physics step, a particle system).  The top level's topology stays (child references, `order`, hence node_count, height and
+ * spill_levels of racc_hip_world_info); the per-instance inverse transforms, the child boxes of the top-level records and ray_pad are
+ * recomputed by the rule of racc_host_world_refit (below, "host world refit"), bit for bit.  A refitted world traces the moved instances
+ * correctly — every result is what a world created with the new transforms reports; how FAST it traces them depends on how far the
+ * instances moved from where the top level was built: its quality degrades (boxes of one subtree grow and overlap; instances that swap
+ * places are the worst case).  racc_hip_world_update rebuilds the top level — "refit per frame, rebuild every N frames".
+ *
+ * All refit state lives in the racc_hip_world_refit handle (device memory: 8 B per instance plus 36 B): per `order` position the slot
+ * (2 * device record + side) its box goes to, every top-level record's own slot in its parent, one arrival counter per record, a 64-bit
+ * word for the largest condition number, a counter of disabled instances and the 4-byte word the world kernels read ray_pad from while
+ * the handle lives.  The world's own allocations and racc_hip_world_info::device_bytes do not change.  At most one handle per world (a
+ * second racc_hip_world_refit_create is RACC_HIP_ERR_INVALID); destroy the handle before its world (racc_hip_world_destroy refuses a
+ * world that still has one).  racc_hip_world_update on a world with a live handle works as before and ends by rebuilding the handle's
+ * tables from the new topology.
+ *
+ * racc_hip_world_refit_device: `count` (= the world's) device-resident 3x4 transforms, 16-byte aligned, asynchronous on `stream`
+ * (hipStream_t as void*, NULL = the default stream).  The member scenes' root boxes are read from their device records, so a member
+ * scene that was refitted (racc_hip_scene_refit*) is picked up with no host step.  The transforms are NOT validated on the host.  An
+ * instance whose transform or boxes racc_host_world_prepare would refuse — a coefficient that is not finite, a determinant that is zero
+ * or not finite in double, a coefficient of the inverse or of the world box that is not finite in float — is DISABLED: its inv becomes
+ * twelve NaNs (every transformed ray is rejected, so it is never reported), its world box {+inf, +inf, +inf, -inf, -inf, -inf}, it does
+ * not enter ray_pad and it is counted; the topology is never written, whatever the input.  racc_hip_world_refit_check returns the count
+ * of the last refit; the caller has synchronised the stream first.
+ * Ordering contract: before the call the caller guarantees that every launch on this world (and every refit of a member scene) issued
+ * on ANOTHER stream has been waited for.  Launches issued afterwards on the SAME stream need nothing; on other streams they need
+ * racc_hip_stream_synchronize on the refit's stream first.
+ * racc_hip_world_refit: host transforms, validated with the host rule (whatever racc_host_world_prepare refuses is refused, and the
+ * world is left as it was); calls racc_hip_synchronize(ctx), copies, runs on a stream of the handle's own and has completed on return.
+ * racc_hip_world_download (any world, with or without a handle): inv [count][12], the top-level records converted back to the 64-byte
+ * blob layout (node_capacity in records, at least node_count of racc_hip_world_info; kind and parent are written as 0 and are
+ * unspecified: the device does not hold them), order [count] and the current ray_pad.  Any output pointer may be NULL.  Blocking; the
+ * caller has waited for whatever writes the world.
+ * Out of scope: a device-side rebuild of the top level, device groups, the racc:: C++ interface, instance masks. */
+struct racc_hip_world_refit;      /* the handle; no typedef, because racc_hip_world_refit is also the name of the blocking entry: write `struct racc_hip_world_refit*` */
+int racc_hip_world_refit_create(racc_hip_ctx*, racc_hip_world*, struct racc_hip_world_refit** out);
+int racc_hip_world_refit_destroy(racc_hip_ctx*, struct racc_hip_world_refit*);
+int racc_hip_world_refit_device(racc_hip_ctx*, struct racc_hip_world_refit*, const void* d_transforms12, uint32_t count, void* stream);
+int racc_hip_world_refit(racc_hip_ctx*, struct racc_hip_world_refit*, const float* transforms12, uint32_t count);
+int racc_hip_world_refit_check(racc_hip_ctx*, struct racc_hip_world_refit*, uint32_t* disabled_instances);
+int racc_hip_world_download(racc_hip_ctx*, const racc_hip_world*, float* inv12_out, void* nodes64_out, uint32_t node_capacity,
+                            uint32_t* order_out, float* ray_pad_out);
 
 int racc_hip_get_launch_info(racc_hip_ctx* ctx, uint32_t lane, racc_hip_launch_info* info);
 /* With racc_hip_options::time_kernels: durations (ms, HIP events on the stream each launch went to) of the lane's traversal
@@ -546,6 +592,26 @@ int racc_host_world_prepare(const float* transforms12, const float* root_boxes6,
                             float* inv12_out, float* world_boxes6_out, float* ray_pad_out,
                             void* nodes64_out, uint32_t node_capacity, uint32_t* node_count_out,
                             uint32_t* order_out, uint32_t* height_out);
+
+/* Host world refit: a top-level tree in, the same tree for moved instances out (pure function: no GPU, no handle; outputs may alias
+ * inputs) — the specification racc_hip_world_refit* reproduces bit for bit.  nodes64 / order as racc_host_world_prepare or
+ * racc_hip_world_download deliver them, node_count = max(count - 1, 1).
+ *   inv12_out, world_boxes6_out, *ray_pad_out   exactly what racc_host_world_prepare computes for these transforms and root boxes (one
+ *                function serves both entries)
+ *   nodes64_out  kind, parent, first and last are copied.  A leaf child's box is the world box of order[first] (cnt is always 1); an empty
+ *                reference's box (cnt 0, the one-instance world's last child) is copied from the input; an inner child's box is that child
+ *                node's first-child box (accumulator) with its last-child box by the select of racc_host_blobs_refit:
+ *                min = b < acc ? b : acc, max = b > acc ? b : acc per component (not fmin / fmax)
+ * Refitting a tree racc_host_world_prepare made to the transforms it was made for reproduces it except possibly the sign of a zero
+ * plane: prepare folds a child's box over the instances below it in `order`, this folds it over the tree, and the select keeps whichever
+ * of -0.0 and +0.0 it meets first.
+ * RACC_HIP_ERR_INVALID before any output byte is written: whatever racc_host_world_prepare refuses (a NULL pointer, count == 0,
+ * count > RACC_HIP_WORLD_MAX_INSTANCES, an input that is not finite, a box with min > max, a singular transform), and a malformed
+ * topology: node_count != max(count - 1, 1), a child index >= node_count, a node reached twice or never, a leaf with cnt > 1, a leaf
+ * position >= count (or named twice, or never), `order` not a permutation of [0, count). */
+int racc_host_world_refit(const float* transforms12, const float* root_boxes6, uint32_t count,
+                          const void* nodes64, uint32_t node_count, const uint32_t* order,
+                          float* inv12_out, float* world_boxes6_out, float* ray_pad_out, void* nodes64_out);
 
 /* The device layout racc_hip_scene_upload gives the node blob (for tools and tests; needs no GPU).  Device record, 64 B: words 0-1 =
  * the two child references (re-numbered), words 2-3 unused, then the child boxes as six (min, max) plane pairs: Lx Ly Lz Rx Ry Rz.

@@ -13,4 +13,6 @@
 #include <array>
 #include "racc_world.inc"
 #include "racc_world_occlusion.inc"
+#include "racc_world_rule.h"
+#include "racc_world_refit.inc"
 #include "racc_wide_format.inc"

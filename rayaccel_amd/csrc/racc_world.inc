@@ -53,6 +53,7 @@ struct WorldArgs {
     const float4* inv;         // three rows per instance
     const WorldInstDev* table;
     float rayPad;
+    const float* rayPadDev;    // the device word that holds the pad while the world has a refit handle (racc_world_refit.inc), else NULL
     uint32_t* spillTop;        // [topSpillLevels][gridThreads]
     uint32_t* spillBot;        // [botSpillLevels][gridThreads]
     uint32_t topSpillLevels, botSpillLevels, spillStride;
@@ -202,7 +203,7 @@ __global__ void __launch_bounds__(kWorldBlock) worldIntersectKernel(const WorldA
                 a.results[idx] = make_float4(__uint_as_float(kInvalidTriangle), 0.0f, 0.0f, 0.0f);
                 a.instances[idx] = kWorldNoInst;
             } else {
-                setWorldRay(w, q0, q1, a.rayPad);
+                setWorldRay(w, q0, q1, a.rayPadDev ? *a.rayPadDev : a.rayPad);
                 bestInst = kWorldNoInst; bestIndex = -1; bestT = bestU = bestV = 0.0f;
                 tCull = w.tMax;
                 rayIdx = idx;
@@ -263,14 +264,19 @@ struct racc_hip_world {
     float rayPad = 0.0f;
     uint32_t maxBottomHeight = 0;
     racc_hip_world_info info{};
+    struct racc_hip_world_refit* refit = nullptr;    // the world's refit handle, if it has one (racc_world_refit.inc) ...
+    float* rayPadDev = nullptr;               // ... and then the handle's device word that holds the current pad
 };
 
 namespace {
 
-// Reads the member scenes' root boxes from the device, runs racc_host_world_prepare and uploads its products.  Blocking.
-int worldCommit(racc_hip_world* w, const float* transforms12) try {
+// racc_world_refit.inc: the handle's tables rebuilt from a new top level (`dev` = its device records on the host) and its pad word set.
+int worldRefitRebuild(racc_hip_world* w, const uint32_t* dev, float rayPad);
+
+// The member scenes' root boxes [count][6], read from the device: record 0's two child boxes combined.
+int worldRootBoxes(const racc_hip_world* w, std::vector<float>& rootBoxes) {
     const uint32_t count = w->count;
-    std::vector<float> rootBoxes(size_t(count) * 6);
+    rootBoxes.resize(size_t(count) * 6);
     std::vector<std::pair<const racc_hip_scene*, std::array<float, 6>>> seen;
     for (uint32_t i = 0; i < count; ++i) {
         const racc_hip_scene* s = w->scenes[i];
@@ -289,6 +295,14 @@ int worldCommit(racc_hip_world* w, const float* transforms12) try {
         }
         std::memcpy(&rootBoxes[size_t(i) * 6], box->data(), 24);
     }
+    return RACC_HIP_OK;
+}
+
+// Reads the member scenes' root boxes from the device, runs racc_host_world_prepare and uploads its products.  Blocking.
+int worldCommit(racc_hip_world* w, const float* transforms12) try {
+    const uint32_t count = w->count;
+    std::vector<float> rootBoxes;
+    if (int rc = worldRootBoxes(w, rootBoxes)) return rc;
     const uint32_t capacity = count > 1u ? count - 1u : 1u;
     std::vector<float> inv(size_t(count) * 12), worldBoxes(size_t(count) * 6);
     std::vector<uint32_t> blob(size_t(capacity) * 16), order(count);
@@ -311,6 +325,7 @@ int worldCommit(racc_hip_world* w, const float* transforms12) try {
     w->info.node_count = nodeCount;
     w->info.height = height;
     w->info.spill_levels = height + 1u > uint32_t(kWorldTopLds) ? height + 1u - uint32_t(kWorldTopLds) : 0u;
+    if (w->refit) return worldRefitRebuild(w, dev.data(), rayPad);      // a live refit handle follows the new topology and pad
     return RACC_HIP_OK;
 } catch (const std::bad_alloc&) {
     return fail(RACC_HIP_ERR_NOMEM, "world: out of host memory");
@@ -325,7 +340,7 @@ int launchOnWorld(racc_hip_ctx* ctx, const racc_hip_world* w, const void* dRays,
     if (int rc = queryGrid(ctx, count, uint32_t(kWorldBlock), waves, limitMsg, g, a.feed)) return rc;
     a.rays = static_cast<const float4*>(dRays);
     a.topNodes = w->topNodes; a.order = w->order; a.inv = w->inv; a.table = w->table;
-    a.rayPad = w->rayPad;
+    a.rayPad = w->rayPad; a.rayPadDev = w->rayPadDev;
     a.topSpillLevels = w->info.spill_levels;
     a.botSpillLevels = w->info.bottom_spill_levels;
     a.spillStride = g.gridThreads;
@@ -360,6 +375,7 @@ extern "C" {
 int racc_hip_world_destroy(racc_hip_ctx* ctx, racc_hip_world* w) {
     if (!ctx) return fail(RACC_HIP_ERR_INVALID, "world_destroy: ctx is NULL");
     if (!w) return RACC_HIP_OK;
+    if (w->refit) return fail(RACC_HIP_ERR_INVALID, "world_destroy: the world has a refit handle: racc_hip_world_refit_destroy comes first");
     hipSetDevice(ctx->device);
     if (w->topNodes) hipFree(w->topNodes);
     if (w->order) hipFree(w->order);

@@ -37,6 +37,7 @@ struct WorldOccArgs {          // WorldArgs with one byte per ray for its two ou
     const float4* inv;
     const WorldInstDev* table;
     float rayPad;
+    const float* rayPadDev;
     uint32_t* spillTop;        // [topSpillLevels][gridThreads]
     uint32_t* spillBot;        // [botSpillLevels][gridThreads]
     uint32_t topSpillLevels, botSpillLevels, spillStride;
@@ -85,7 +86,7 @@ __global__ void __launch_bounds__(kWorldBlock) worldOccludedKernel(const WorldOc
             float4 q0, q1;
             if (!admitRay(a.rays, idx, q0, q1)) a.occluded[idx] = uint8_t(0);
             else {
-                setWorldRay(w, q0, q1, a.rayPad);
+                setWorldRay(w, q0, q1, a.rayPadDev ? *a.rayPadDev : a.rayPad);
                 tEnd = worldWidenedEnd(w.tMax);
                 rayIdx = idx;
                 inBot = false;

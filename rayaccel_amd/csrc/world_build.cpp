@@ -20,12 +20,14 @@
 // 1 << 24.  Median split of the box centres along the longest axis of their bounds, ties by instance index: deterministic.  A world of
 // one instance has a root whose last child is the empty reference 0 (count 0; the kernel never enters it).
 #include "racc_hip.h"
+#include "racc_world_rule.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include <vector>
 
@@ -36,16 +38,50 @@ namespace {
 struct Node64 { uint32_t kind, parent, first, last; float box[12]; };      // leftMin[3], leftMax[3], rightMin[3], rightMax[3]
 static_assert(sizeof(Node64) == 64, "reference record size");
 
-int refuse(int code, const char* what, long long at = -1) {
+const char* const kPrepare = "racc_host_world_prepare";
+const char* const kRefit = "racc_host_world_refit";
+
+// `who` = the entry the message names
+int refuse(const char* who, int code, const char* what, long long at = -1) {
     char msg[256];
-    if (at >= 0) std::snprintf(msg, sizeof(msg), "racc_host_world_prepare: %s (instance %lld)", what, at);
-    else std::snprintf(msg, sizeof(msg), "racc_host_world_prepare: %s", what);
+    if (at >= 0) std::snprintf(msg, sizeof(msg), "%s: %s (instance %lld)", who, what, at);
+    else std::snprintf(msg, sizeof(msg), "%s: %s", who, what);
     racc_hip_set_error_(msg);
     return code;
 }
 
-inline float roundDown(double x) { const float f = float(x); return double(f) > x ? std::nextafterf(f, -INFINITY) : f; }
-inline float roundUp(double x) { const float f = float(x); return double(f) < x ? std::nextafterf(f, INFINITY) : f; }
+// What every entry refuses about its inputs' shape, before anything is read.
+int refuseShape(const char* who, const float* transforms12, const float* rootBoxes6, uint32_t count) {
+    if (!transforms12 || !rootBoxes6) return refuse(who, RACC_HIP_ERR_INVALID, "transforms / root boxes pointer is NULL");
+    if (!count) return refuse(who, RACC_HIP_ERR_INVALID, "count is 0: a world has at least one instance");
+    if (count > RACC_HIP_WORLD_MAX_INSTANCES) return refuse(who, RACC_HIP_ERR_INVALID, "more than 2^20 instances");
+    return RACC_HIP_OK;
+}
+
+// The per-instance part of racc_host_world_prepare and racc_host_world_refit (and what racc_hip_world_refit validates with): inverses,
+// world boxes and the ray pad by racc_world_rule.h, into the caller's own buffers; a refusal names `who` and the instance.
+int perInstance(const char* who, const float* transforms12, const float* rootBoxes6, uint32_t count, float* inv, float* boxes, float& rayPad) {
+    namespace rule = racc_world_rule;
+    static const char* const kWhy[] = {
+        "",
+        "a transform coefficient is not finite",
+        "a root box coordinate is not finite",
+        "a root box has min > max",
+        "a transform is singular (its double-precision determinant is zero or not finite)",
+        "a transform is singular in float (a coefficient of its inverse is not finite)",
+        "a world-space box is not finite in float",
+    };
+    double maxCond = 0.0;
+    for (uint32_t i = 0; i < count; ++i) {
+        double cond = 0.0;
+        const rule::Refusal why = rule::instance(transforms12 + size_t(i) * 12, rootBoxes6 + size_t(i) * 6, inv + size_t(i) * 12, boxes + size_t(i) * 6, cond);
+        if (why != rule::kOk) return refuse(who, RACC_HIP_ERR_INVALID, kWhy[why], i);
+        maxCond = std::max(maxCond, cond);
+    }
+    rayPad = rule::rayPadOf(maxCond);
+    if (!std::isfinite(rayPad)) return refuse(who, RACC_HIP_ERR_INVALID, "the transforms' condition numbers overflow float");
+    return RACC_HIP_OK;
+}
 
 struct Builder {
     const float* boxes;                 // [count][6] min, max
@@ -100,66 +136,17 @@ extern "C" int racc_host_world_prepare(const float* transforms12, const float* r
                                        float* inv12_out, float* world_boxes6_out, float* ray_pad_out,
                                        void* nodes64_out, uint32_t node_capacity, uint32_t* node_count_out,
                                        uint32_t* order_out, uint32_t* height_out) try {
-    if (!transforms12 || !root_boxes6) return refuse(RACC_HIP_ERR_INVALID, "transforms / root boxes pointer is NULL");
-    if (!inv12_out || !world_boxes6_out || !ray_pad_out || !nodes64_out || !node_count_out || !order_out || !height_out) return refuse(RACC_HIP_ERR_INVALID, "an output pointer is NULL");
-    if (!count) return refuse(RACC_HIP_ERR_INVALID, "count is 0: a world has at least one instance");
-    if (count > RACC_HIP_WORLD_MAX_INSTANCES) return refuse(RACC_HIP_ERR_INVALID, "more than 2^20 instances");
+    if (!transforms12 || !root_boxes6) return refuse(kPrepare, RACC_HIP_ERR_INVALID, "transforms / root boxes pointer is NULL");
+    if (!inv12_out || !world_boxes6_out || !ray_pad_out || !nodes64_out || !node_count_out || !order_out || !height_out) return refuse(kPrepare, RACC_HIP_ERR_INVALID, "an output pointer is NULL");
+    if (!count) return refuse(kPrepare, RACC_HIP_ERR_INVALID, "count is 0: a world has at least one instance");
+    if (count > RACC_HIP_WORLD_MAX_INSTANCES) return refuse(kPrepare, RACC_HIP_ERR_INVALID, "more than 2^20 instances");
     const uint32_t nodesNeeded = count > 1u ? count - 1u : 1u;
-    if (node_capacity < nodesNeeded) return refuse(RACC_HIP_ERR_INVALID, "node_capacity is below max(count - 1, 1)");
+    if (node_capacity < nodesNeeded) return refuse(kPrepare, RACC_HIP_ERR_INVALID, "node_capacity is below max(count - 1, 1)");
 
     // everything is validated and computed into buffers of our own before the first output byte is written
     std::vector<float> inv(size_t(count) * 12), boxes(size_t(count) * 6);
-    const double K = 1.0 / 1048576.0;      // 2^-20, see the head of this file
-    double maxCond = 0.0;
-    for (uint32_t i = 0; i < count; ++i) {
-        const float* m = transforms12 + size_t(i) * 12;
-        const float* rb = root_boxes6 + size_t(i) * 6;
-        for (int k = 0; k < 12; ++k) if (!std::isfinite(m[k])) return refuse(RACC_HIP_ERR_INVALID, "a transform coefficient is not finite", i);
-        for (int k = 0; k < 6; ++k) if (!std::isfinite(rb[k])) return refuse(RACC_HIP_ERR_INVALID, "a root box coordinate is not finite", i);
-        for (int k = 0; k < 3; ++k) if (rb[k] > rb[3 + k]) return refuse(RACC_HIP_ERR_INVALID, "a root box has min > max", i);
-        const double a[3][3] = { { m[0], m[1], m[2] }, { m[4], m[5], m[6] }, { m[8], m[9], m[10] } };
-        const double b[3] = { m[3], m[7], m[11] };
-        double c[3][3];      // cofactors: c[r][k] = cofactor of a[r][k]
-        for (int r = 0; r < 3; ++r)
-            for (int k = 0; k < 3; ++k) {
-                const int r1 = (r + 1) % 3, r2 = (r + 2) % 3, k1 = (k + 1) % 3, k2 = (k + 2) % 3;
-                c[r][k] = a[r1][k1] * a[r2][k2] - a[r1][k2] * a[r2][k1];
-            }
-        const double det = a[0][0] * c[0][0] + a[0][1] * c[0][1] + a[0][2] * c[0][2];
-        if (det == 0.0 || !std::isfinite(det)) return refuse(RACC_HIP_ERR_INVALID, "a transform is singular (its double-precision determinant is zero or not finite)", i);
-        double B[3][3], t[3], normA = 0.0, normB = 0.0, normb = 0.0;
-        for (int r = 0; r < 3; ++r) for (int k = 0; k < 3; ++k) B[r][k] = c[k][r] / det;      // adjugate = transposed cofactors
-        for (int r = 0; r < 3; ++r) t[r] = -((B[r][0] * b[0] + B[r][1] * b[1]) + B[r][2] * b[2]);
-        float* o = &inv[size_t(i) * 12];
-        for (int r = 0; r < 3; ++r) {
-            o[r * 4 + 0] = float(B[r][0]); o[r * 4 + 1] = float(B[r][1]); o[r * 4 + 2] = float(B[r][2]); o[r * 4 + 3] = float(t[r]);
-            for (int k = 0; k < 4; ++k) if (!std::isfinite(o[r * 4 + k])) return refuse(RACC_HIP_ERR_INVALID, "a transform is singular in float (a coefficient of its inverse is not finite)", i);
-            normA = std::max(normA, std::fabs(a[r][0]) + std::fabs(a[r][1]) + std::fabs(a[r][2]));
-            normB = std::max(normB, std::fabs(B[r][0]) + std::fabs(B[r][1]) + std::fabs(B[r][2]));
-            normb = std::max(normb, std::fabs(b[r]));
-        }
-        const double cond = normA * normB;
-        maxCond = std::max(maxCond, cond);
-        // the eight corners in double: per world axis the extremes are reached by picking min or max per object axis
-        double lo[3], hi[3], mag = 0.0;
-        for (int r = 0; r < 3; ++r) {
-            lo[r] = hi[r] = b[r];
-            for (int k = 0; k < 3; ++k) {
-                const double p = a[r][k] * double(rb[k]), q = a[r][k] * double(rb[3 + k]);
-                lo[r] += std::min(p, q); hi[r] += std::max(p, q);
-            }
-            mag = std::max(mag, std::max(std::fabs(lo[r]), std::fabs(hi[r])));
-        }
-        const double margin = K * cond * (normb + mag);
-        float* w = &boxes[size_t(i) * 6];
-        for (int r = 0; r < 3; ++r) {
-            // (the sums above carry a few double roundings of their own: 2^-40 of the magnitudes, far inside the margin)
-            w[r] = roundDown(lo[r] - margin); w[3 + r] = roundUp(hi[r] + margin);
-            if (!std::isfinite(w[r]) || !std::isfinite(w[3 + r])) return refuse(RACC_HIP_ERR_INVALID, "a world-space box is not finite in float", i);
-        }
-    }
-    const float rayPad = roundUp(2.0 * K * maxCond);
-    if (!std::isfinite(rayPad)) return refuse(RACC_HIP_ERR_INVALID, "the transforms' condition numbers overflow float");
+    float rayPad = 0.0f;
+    if (int rc = perInstance(kPrepare, transforms12, root_boxes6, count, inv.data(), boxes.data(), rayPad)) return rc;
 
     std::vector<uint32_t> order(count);
     for (uint32_t i = 0; i < count; ++i) order[i] = i;
@@ -188,5 +175,87 @@ extern "C" int racc_host_world_prepare(const float* transforms12, const float* r
     *height_out = height;
     return RACC_HIP_OK;
 } catch (const std::bad_alloc&) {
-    return refuse(RACC_HIP_ERR_NOMEM, "out of host memory");
+    return refuse(kPrepare, RACC_HIP_ERR_NOMEM, "out of host memory");
+}
+
+// Internal (not in the header): the per-instance rule for racc_hip_world_refit (racc_world_refit.inc), whose refusals name `who`.
+// inv12_out / world_boxes6_out are scratch of the caller's; nothing else is written.
+extern "C" int racc_host_world_instances_(const char* who, const float* transforms12, const float* root_boxes6, uint32_t count,
+                                          float* inv12_out, float* world_boxes6_out, float* ray_pad_out) {
+    if (int rc = refuseShape(who, transforms12, root_boxes6, count)) return rc;
+    if (!inv12_out || !world_boxes6_out || !ray_pad_out) return refuse(who, RACC_HIP_ERR_INVALID, "an output pointer is NULL");
+    return perInstance(who, transforms12, root_boxes6, count, inv12_out, world_boxes6_out, *ray_pad_out);
+}
+
+extern "C" int racc_host_world_refit(const float* transforms12, const float* root_boxes6, uint32_t count,
+                                     const void* nodes64, uint32_t node_count, const uint32_t* order,
+                                     float* inv12_out, float* world_boxes6_out, float* ray_pad_out, void* nodes64_out) try {
+    if (int rc = refuseShape(kRefit, transforms12, root_boxes6, count)) return rc;
+    if (!nodes64 || !order) return refuse(kRefit, RACC_HIP_ERR_INVALID, "nodes / order pointer is NULL");
+    if (!inv12_out || !world_boxes6_out || !ray_pad_out || !nodes64_out) return refuse(kRefit, RACC_HIP_ERR_INVALID, "an output pointer is NULL");
+    if (node_count != (count > 1u ? count - 1u : 1u)) return refuse(kRefit, RACC_HIP_ERR_INVALID, "node_count is not max(count - 1, 1)");
+
+    // everything is validated and computed into buffers of our own before the first output byte is written (outputs may alias inputs)
+    std::vector<float> inv(size_t(count) * 12), boxes(size_t(count) * 6);
+    float rayPad = 0.0f;
+    if (int rc = perInstance(kRefit, transforms12, root_boxes6, count, inv.data(), boxes.data(), rayPad)) return rc;
+
+    std::vector<Node64> nodes(node_count);
+    std::memcpy(nodes.data(), nodes64, size_t(node_count) * sizeof(Node64));
+    std::vector<uint8_t> seen(count, 0);
+    for (uint32_t i = 0; i < count; ++i) {
+        if (order[i] >= count || seen[order[i]]) return refuse(kRefit, RACC_HIP_ERR_INVALID, "order is not a permutation of [0, count)");
+        seen[order[i]] = 1;
+    }
+    // the topology, walked from the root: every node reached exactly once, every position of `order` in exactly one leaf
+    std::vector<uint8_t> nodeSeen(node_count, 0), posSeen(count, 0);
+    std::vector<uint32_t> visit;      // parents before their children
+    visit.reserve(node_count);
+    visit.push_back(0u);
+    nodeSeen[0] = 1;
+    for (size_t at = 0; at < visit.size(); ++at) {
+        const Node64& n = nodes[visit[at]];
+        for (const uint32_t c : { n.first, n.last }) {
+            if (c & 0x80000000u) {
+                const uint32_t i = c & 0x7FFFFFFFu;
+                if (i >= node_count) return refuse(kRefit, RACC_HIP_ERR_INVALID, "a child index is not below node_count");
+                if (nodeSeen[i]) return refuse(kRefit, RACC_HIP_ERR_INVALID, "a node is reached twice");
+                nodeSeen[i] = 1;
+                visit.push_back(i);
+            } else {
+                const uint32_t first = c & 0xFFFFFFu, cnt = c >> 24;
+                if (cnt > 1u) return refuse(kRefit, RACC_HIP_ERR_INVALID, "a leaf names more than one instance");
+                if (cnt == 0u) continue;      // the empty reference (a one-instance world's last child): its box is kept
+                if (first >= count) return refuse(kRefit, RACC_HIP_ERR_INVALID, "a leaf position is not below count");
+                if (posSeen[first]) return refuse(kRefit, RACC_HIP_ERR_INVALID, "a leaf position is named twice");
+                posSeen[first] = 1;
+            }
+        }
+    }
+    if (visit.size() != node_count) return refuse(kRefit, RACC_HIP_ERR_INVALID, "a node is never reached from the root");
+    for (uint32_t i = 0; i < count; ++i) if (!posSeen[i]) return refuse(kRefit, RACC_HIP_ERR_INVALID, "a position of order is in no leaf");
+
+    // boxes bottom-up: children before their parents
+    for (size_t at = visit.size(); at-- > 0;) {
+        Node64& n = nodes[visit[at]];
+        for (int side = 0; side < 2; ++side) {
+            const uint32_t c = side ? n.last : n.first;
+            float* box = n.box + side * 6;
+            if (c & 0x80000000u) {
+                const float* acc = nodes[c & 0x7FFFFFFFu].box;      // the child's first-child box (accumulator), then its last-child box
+                const float* b = acc + 6;
+                for (int k = 0; k < 3; ++k) { box[k] = b[k] < acc[k] ? b[k] : acc[k]; box[3 + k] = b[3 + k] > acc[3 + k] ? b[3 + k] : acc[3 + k]; }
+            } else if (c >> 24) {
+                std::memcpy(box, &boxes[size_t(order[c & 0xFFFFFFu]) * 6], 24);
+            }
+        }
+    }
+
+    std::memcpy(inv12_out, inv.data(), inv.size() * sizeof(float));
+    std::memcpy(world_boxes6_out, boxes.data(), boxes.size() * sizeof(float));
+    *ray_pad_out = rayPad;
+    std::memcpy(nodes64_out, nodes.data(), nodes.size() * sizeof(Node64));
+    return RACC_HIP_OK;
+} catch (const std::bad_alloc&) {
+    return refuse(kRefit, RACC_HIP_ERR_NOMEM, "out of host memory");
 }

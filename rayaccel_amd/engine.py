@@ -103,6 +103,12 @@ ABI = {
     "racc_hip_world_intersect": (_i, [_vp, _vp, _vp, _vp, _vp, _u32]),
     "racc_hip_world_occluded_device": (_i, [_vp, _vp, _vp, _vp, _u32, _vp]),
     "racc_hip_world_occluded": (_i, [_vp, _vp, _vp, _vp, _u32]),
+    "racc_hip_world_refit_create": (_i, [_vp, _vp, _P(_vp)]),
+    "racc_hip_world_refit_destroy": (_i, [_vp, _vp]),
+    "racc_hip_world_refit_device": (_i, [_vp, _vp, _vp, _u32, _vp]),
+    "racc_hip_world_refit": (_i, [_vp, _vp, _vp, _u32]),
+    "racc_hip_world_refit_check": (_i, [_vp, _vp, _P(_u32)]),
+    "racc_hip_world_download": (_i, [_vp, _vp, _vp, _vp, _u32, _vp, _P(C.c_float)]),
     "racc_hip_get_launch_info": (_i, [_vp, _u32, _P(LaunchInfo)]),
     "racc_hip_read_kernel_times": (_i, [_vp, _u32, _P(C.c_float), _u32, _P(_u32)]),
     "racc_hip_read_stats": (_i, [_vp, _u32, _P(_u64), _i]),
@@ -137,6 +143,7 @@ ABI = {
     "racc_host_scene_bvh2": (_i, [_vp, _P(_vp), _P(_u32), _P(_vp), _P(_u32)]),
     "racc_host_blobs_refit": (_i, [_vp, _u32, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _vp]),
     "racc_host_world_prepare": (_i, [_vp, _vp, _u32, _vp, _vp, _P(C.c_float), _vp, _u32, _P(_u32), _vp, _P(_u32)]),
+    "racc_host_world_refit": (_i, [_vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _P(C.c_float), _vp]),
     "racc_host_scene_device_nodes": (_i, [_vp, _u32, _u32, _u32, _i, _vp, _u32, _P(_u32)]),
     "racc_host_scene_wide_nodes": (_i, [_vp, _u32, _u32, _u32, _i, _vp, _u32, _P(_u32), _P(_u32)]),
 }
@@ -348,12 +355,64 @@ def host_world_prepare(transforms, root_boxes):
     return dict(inv=inv.reshape(n, 3, 4), world_boxes=boxes, ray_pad=float(pad.value), nodes=nodes[:nn.value].copy(), order=order[:n], height=int(height.value))
 
 
+def host_world_refit(transforms, root_boxes, nodes, order):
+    """racc_host_world_refit: the top-level tree (`nodes`, `order` as host_world_prepare or World.download deliver them) refitted to
+    `transforms` — topology kept, inverses / world boxes / ray_pad as host_world_prepare computes them.  No GPU needed.  Returns
+    dict(inv [N,3,4], world_boxes [N,6], ray_pad, nodes, order)."""
+    t = _as_transforms(transforms)
+    rb = np.ascontiguousarray(root_boxes, dtype=np.float32).reshape(-1, 6)
+    if len(rb) != len(t):
+        raise ValueError("one root box per transform")
+    n = len(t)
+    nodes = np.ascontiguousarray(nodes)
+    order = np.ascontiguousarray(order, dtype=np.uint32)
+    assert nodes.dtype.itemsize == 64
+    if len(order) != n:
+        raise ValueError("one position of order per transform")
+    inv, boxes, out_nodes = np.zeros((n, 12), np.float32), np.zeros((n, 6), np.float32), np.zeros_like(nodes)
+    pad = C.c_float(0)
+    _check(load_library().racc_host_world_refit(_ptr(t), _ptr(rb), n, _ptr(nodes), len(nodes), _ptr(order), _ptr(inv), _ptr(boxes), C.byref(pad), _ptr(out_nodes)))
+    return dict(inv=inv.reshape(n, 3, 4), world_boxes=boxes, ray_pad=float(pad.value), nodes=out_nodes, order=order.copy())
+
+
+class WorldRefit:
+    """racc_hip_world_refit: what it takes to refit a world's top level to moved instances on the device (World.create_refit).  The
+    topology stays, so the top level's quality degrades as instances move away from where it was built; World.update rebuilds it.
+    Destroy it before its world."""
+
+    def __init__(self, world, handle):
+        self._world, self._ctx, self._h = world, world._ctx, handle
+
+    def refit(self, transforms):
+        """Host transforms [N,3,4], validated, blocking (racc_hip_world_refit): waits for everything the context has in flight first."""
+        t = _as_transforms(transforms)
+        _check(load_library().racc_hip_world_refit(self._ctx._h, self._h, _ptr(t), len(t)))
+
+    def refit_device(self, d_transforms, stream=None):
+        """Device-resident transforms (one per instance of the world, 48 B each), asynchronous on `stream` (racc_hip_world_refit_device):
+        not validated — an unusable transform disables its instance (check()); launches on the world issued later on the same stream
+        need no wait."""
+        _check(load_library().racc_hip_world_refit_device(self._ctx._h, self._h, d_transforms, self._world.count, stream))
+
+    def check(self):
+        """How many instances the last refit disabled (racc_hip_world_refit_check); synchronise the refit's stream first."""
+        n = C.c_uint32(0)
+        _check(load_library().racc_hip_world_refit_check(self._ctx._h, self._h, C.byref(n)))
+        return int(n.value)
+
+    def destroy(self):
+        if self._h:
+            load_library().racc_hip_world_refit_destroy(self._ctx._h, self._h)
+            self._h = None
+
+
 class World:
     """racc_hip_world: an ordered list of (object-to-world transform, Scene) instances (Context.create_world; no reference counterpart).
     It borrows its scenes: destroy it before any of them."""
 
     def __init__(self, ctx, handle, scenes):
         self._ctx, self._h, self._scenes = ctx, handle, list(scenes)
+        self.count = len(self._scenes)
 
     @property
     def info(self):
@@ -399,6 +458,21 @@ class World:
         """New transforms for the same scenes — also the call to make after a member scene was refitted.  Blocking (racc_hip_world_update)."""
         t = _as_transforms(transforms)
         _check(load_library().racc_hip_world_update(self._ctx._h, self._h, _ptr(t), len(t)))
+
+    def create_refit(self):
+        """racc_hip_world_refit_create: the handle that refits this world's top level on the device (at most one per world)."""
+        h = C.c_void_p()
+        _check(load_library().racc_hip_world_refit_create(self._ctx._h, self._h, C.byref(h)))
+        return WorldRefit(self, h)
+
+    def download(self):
+        """racc_hip_world_download: dict(inv [N,3,4], nodes (top level, GPU_NODE_DTYPE; kind and parent unspecified), order [N], ray_pad)
+        as the device holds them now.  Blocking; wait for whatever writes the world first."""
+        n = self.count
+        inv, nodes, order = np.zeros((n, 12), np.float32), np.zeros(self.info["node_count"], GPU_NODE_DTYPE), np.zeros(n, np.uint32)
+        pad = C.c_float(0)
+        _check(load_library().racc_hip_world_download(self._ctx._h, self._h, _ptr(inv), _ptr(nodes), len(nodes), _ptr(order), C.byref(pad)))
+        return dict(inv=inv.reshape(n, 3, 4), nodes=nodes, order=order, ray_pad=float(pad.value))
 
     def destroy(self):
         if self._h:
