@@ -288,7 +288,8 @@ int racc_hip_occluded(racc_hip_ctx*, const racc_hip_scene*, const void* rays, ui
  * racc_hip_refit_create: indices / index_count as the scene was built from, vertex_count = the length of every vertex array to come.
  * Validates like the host refit (remap's triangle ids < index_count / 3, every index < vertex_count).  RACC_HIP_ERR_INVALID, scene
  * untouched, when the scene carries a 4-wide, compressed or SoA copy of the tree — a context created with kernel_variant 45 or 50,
- * wide_below != 0 or the SoA variant: those copies are not refitted and a stale one would give wrong hits — or is a device group's replica.
+ * wide_below != 0 or the SoA variant: this entry does not refit those copies and a stale one would give wrong hits (racc_hip_refit_create_wide,
+ * below, takes the 4-wide and compressed ones) — or is a device group's replica.
  *
  * Ordering contract: a refit rewrites arrays that traversal kernels read.
  *   racc_hip_scene_refit (host xyzw vertices, validated: finite) calls racc_hip_synchronize(ctx) first, so that no kernel of a chain is
@@ -305,6 +306,28 @@ int racc_hip_refit_destroy(racc_hip_ctx*, racc_hip_refit*);
 int racc_hip_scene_refit(racc_hip_ctx*, racc_hip_refit*, const float* vertices, uint32_t vertex_count);
 int racc_hip_scene_refit_device(racc_hip_ctx*, racc_hip_refit*, const void* d_vertices, uint32_t vertex_count, void* stream);
 int racc_hip_refit_download(racc_hip_ctx*, racc_hip_refit*, void* nodes64_out, uint32_t node_capacity, void* pairs48_out, uint32_t pair_capacity);
+
+/* ---- dynamic scenes: refit of the 4-wide and compressed copies (fast mode) ----
+ * racc_hip_refit_create_wide is racc_hip_refit_create for a scene that carries a 4-wide and / or a compressed copy of the tree — a
+ * context created with kernel_variant 45-53 or wide_below != 0.  The handle is an ordinary racc_hip_refit: racc_hip_scene_refit,
+ * racc_hip_scene_refit_device, racc_hip_refit_download and racc_hip_refit_destroy work on it with the ordering contract above, and
+ * every refit also rewrites whichever wide copies the scene has, by the rule of racc_host_scene_wide_nodes_refit (below, "host wide
+ * refit"), bit for bit: the collapse stays as the upload made it, every plane follows the refitted binary boxes.  Quality degrades with
+ * motion as the binary tree's does — and in one more way: which four boxes share a record was decided by the areas at upload.
+ * RACC_HIP_ERR_INVALID, scene untouched: an SoA copy, a device group's replica, a scene without topology words or without any wide
+ * copy, a scene that already has a wide handle (at most one per scene; racc_hip_refit_create refuses these scenes as before), or wide
+ * references on the device that are not what the collapse of the device's binary records gives (the handle replays it at creation).
+ * Device memory on top of the plain handle's: 16 B per wide record.
+ * A compressed frame that cannot hold its boxes — a plane that is not finite, an extent that overflows binary32 — is DISABLED by the
+ * refit: references kept, every slot written as an unused one, origin +inf, so that every plane decodes to +inf and rays miss the
+ * subtree below it.  racc_hip_refit_check returns how many frames the last refit disabled (0 on a plain handle); the caller has
+ * synchronised first.  The blocking racc_hip_scene_refit never gets there: on a handle whose scene has a compressed copy it returns
+ * RACC_HIP_ERR_LIMIT, scene untouched, when max - min of all vertices on an axis is not finite in binary32.
+ * racc_hip_refit_download_wide: the device's current records of `format` (45: 128 B, 50: 64 B; as racc_host_scene_wide_nodes lays
+ * them out); RACC_HIP_ERR_INVALID when the scene has no copy of that format; out may be NULL (then only *count); capacity in records. */
+int racc_hip_refit_create_wide(racc_hip_ctx*, racc_hip_scene*, const uint32_t* indices, uint32_t index_count, uint32_t vertex_count, racc_hip_refit** out);
+int racc_hip_refit_download_wide(racc_hip_ctx*, racc_hip_refit*, int format, void* out, uint32_t capacity, uint32_t* count);
+int racc_hip_refit_check(racc_hip_ctx*, racc_hip_refit*, uint32_t* disabled_frames);
 
 /* ---- instancing: two-level scenes with per-instance transforms ----
  * ≙ nothing in the reference (one flattened scene per racc::Scene, Scene.cpp:216-349); Embree's RTC_GEOMETRY_TYPE_INSTANCE and the
@@ -639,6 +662,31 @@ int racc_host_scene_device_nodes(const void* nodes64, uint32_t node_count, uint3
  * out may be NULL (then only *count and *stack_bound are returned); capacity in records. */
 int racc_host_scene_wide_nodes(const void* nodes64, uint32_t node_count, uint32_t pair_count, uint32_t remap_count, int format,
                                void* out, uint32_t capacity, uint32_t* count, uint32_t* stack_bound);
+
+/* Host wide refit: the 4-wide records of a refitted scene (pure function: no GPU) — the specification racc_hip_scene_refit* reproduces
+ * bit for bit on a handle of racc_hip_refit_create_wide.
+ *   nodes64_built  the blob the scene was uploaded from.  It alone decides the collapse: which binary child box every slot copies, the
+ *                  slot order, the breadth-first numbering, `used` and the leaf reference in unused slots — racc_host_scene_wide_nodes'
+ *                  collapse of that blob, kept as the binary refit keeps its topology.  The wide tree's quality therefore degrades
+ *                  with motion like the binary tree's, and the grouping of boxes into records no longer follows their areas.
+ *   nodes64_now    the same topology with refitted boxes, as racc_host_blobs_refit delivers them.  It supplies every plane.
+ *   format 45      a used slot's six planes are its source child's box in nodes64_now, lower / upper ordered per axis; references, `used`
+ *                  and unused slots as built.  Holds any box; never disables.
+ *   format 50      the frame of those planes, stated by its result:
+ *                    org    per axis the fold of the used lower planes in slot order, `p < acc ? p : acc` from +inf on (of +0.0 and
+ *                           -0.0 the one met first stays);
+ *                    scale  the correctly rounded binary32 (hi - lo) / 255 with hi the like fold of the upper planes, FLT_MIN if that
+ *                           quotient is not positive, then raised by nextafter until fmaf(255, scale, org) >= hi;
+ *                    a lower byte is the largest a in [0, 255] with fmaf(a, scale, org) <= plane, an upper byte the smallest b with
+ *                    fmaf(b, scale, org) >= plane; unused slots get 255 / 0.
+ *                  A frame with a used plane that is not finite, or whose org or scale is not finite on an axis, is DISABLED and
+ *                  counted in *disabled_frames: references kept, all four slots 255 / 0, org +inf and scale FLT_MIN on every axis
+ *                  (every plane decodes to +inf, format 45's convention for a slot that is never entered: rays miss the subtree).
+ * With nodes64_now == nodes64_built the records equal racc_host_scene_wide_nodes' byte for byte.  RACC_HIP_ERR_INVALID: a NULL pointer,
+ * another format, a blob racc_hip_scene_upload refuses, blobs that differ in a child reference.  out may be NULL (then only *count is
+ * returned; *disabled_frames is 0); capacity in records. */
+int racc_host_scene_wide_nodes_refit(const void* nodes64_built, const void* nodes64_now, uint32_t node_count, uint32_t pair_count, uint32_t remap_count,
+                                     int format, void* out, uint32_t capacity, uint32_t* count, uint32_t* disabled_frames);
 
 #ifdef __cplusplus
 }

@@ -10,6 +10,7 @@
 #include "racc_query.inc"
 #include "racc_occlusion.inc"
 #include "racc_refit.inc"
+#include "racc_refit_wide.inc"
 #include <array>
 #include "racc_world.inc"
 #include "racc_world_occlusion.inc"

@@ -96,9 +96,18 @@ struct racc_hip_refit {
     uint32_t* counters = nullptr;             // [deviceNodes] arrival counters
     float4* vertices = nullptr;               // staging of the blocking entry, allocated at its first call
     hipStream_t stream = nullptr;             // ... and its stream
+    // a handle of racc_hip_refit_create_wide (racc_refit_wide.inc): every refit also rewrites the scene's 4-wide / compressed records
+    bool wideClaimed = false;                 // this handle is the scene's one wide handle (racc_scene_registry.inc)
+    uint32_t wideCount = 0;                   // 0: a plain handle
+    uint4* wideSources = nullptr;             // [wideCount] per slot 2 * device record + side of the binary child box it copies, kWideNone in an unused slot
+    uint32_t* wideDisabled = nullptr;         // [1] compressed frames the last refit disabled (racc_hip_refit_check)
 };
 
 namespace {
+
+int refitWideLaunch(racc_hip_refit* r, hipStream_t st);      // racc_refit_wide.inc
+int refitWideAttach(racc_hip_refit* r);
+void refitWideDetach(racc_hip_refit* r);
 
 int refitLaunch(racc_hip_refit* r, const float4* dVertices, hipStream_t st) {
     const racc_hip_scene* s = r->scene;
@@ -109,6 +118,7 @@ int refitLaunch(racc_hip_refit* r, const float4* dVertices, hipStream_t st) {
     hipLaunchKernelGGL(refitBoxesKernel, dim3((r->leafCount + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, st, dVertices, r->quads, r->leaves, r->leafCount,
                        r->parentSlot, r->counters, reinterpret_cast<float*>(s->nodes));
     HIP_TRY(hipGetLastError(), "launch refitBoxesKernel");
+    if (r->wideCount) return refitWideLaunch(r, st);      // behind the box kernel on the same stream: the kernel boundary publishes the binary boxes
     return RACC_HIP_OK;
 }
 
@@ -126,19 +136,28 @@ int racc_hip_refit_destroy(racc_hip_ctx* ctx, racc_hip_refit* r) {
     if (r->parentSlot) hipFree(r->parentSlot);
     if (r->counters) hipFree(r->counters);
     if (r->vertices) hipFree(r->vertices);
+    refitWideDetach(r);
     delete r;
     return RACC_HIP_OK;
 }
 
-int racc_hip_refit_create(racc_hip_ctx* ctx, racc_hip_scene* scene, const uint32_t* indices, uint32_t index_count, uint32_t vertex_count,
-                          racc_hip_refit** out) try {
+}  // extern "C"
+
+namespace {
+
+// racc_hip_refit_create and racc_hip_refit_create_wide (racc_refit_wide.inc): the latter also attaches the wide state (refitWideAttach)
+int refitCreate(racc_hip_ctx* ctx, racc_hip_scene* scene, const uint32_t* indices, uint32_t index_count, uint32_t vertex_count, bool wide,
+                racc_hip_refit** out) try {
     if (!ctx) return fail(RACC_HIP_ERR_INVALID, "refit_create: ctx is NULL");
     if (!out) return fail(RACC_HIP_ERR_INVALID, "refit_create: out is NULL");
     *out = nullptr;
     if (!scene || !indices) return fail(RACC_HIP_ERR_INVALID, "refit_create: scene/indices is NULL");
-    if (scene->nodesWide || scene->nodesWideQ || scene->nodesSoa)
+    if (!wide && (scene->nodesWide || scene->nodesWideQ || scene->nodesSoa))
         return fail(RACC_HIP_ERR_INVALID, "refit_create: the scene carries a 4-wide, compressed or SoA copy of the tree (kernel_variant 45 / 50, wide_below, the SoA variant); "
-                                          "refit of those formats is not implemented and a stale copy would give wrong hits");
+                                          "racc_hip_refit_create_wide refits the 4-wide and compressed copies, a stale copy would give wrong hits");
+    if (wide && scene->nodesSoa) return fail(RACC_HIP_ERR_INVALID, "refit_create_wide: the scene carries an SoA copy of the tree (the SoA variant), which is not refitted");
+    if (wide && !scene->nodesWide && !scene->nodesWideQ)
+        return fail(RACC_HIP_ERR_INVALID, "refit_create_wide: the scene carries neither a 4-wide nor a compressed copy of the tree (racc_hip_refit_create is the entry for it)");
     std::shared_ptr<const RefitTopology> topo = sceneTopology(scene);
     if (!topo) return fail(RACC_HIP_ERR_INVALID, "refit_create: the blob's topology words were not kept for this scene (a device group's replica, RACC_REFIT_TOPOLOGY=0, or no host memory at upload)");
     if (index_count % 3 != 0) return fail(RACC_HIP_ERR_INVALID, "refit_create: index_count is not a multiple of 3");
@@ -221,10 +240,20 @@ int racc_hip_refit_create(racc_hip_ctx* ctx, racc_hip_scene* scene, const uint32
     if (e == hipSuccess) e = hipMemcpy(r->parentSlot, parentSlot.data(), size_t(deviceNodes) * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking);
     if (e != hipSuccess) { racc_hip_refit_destroy(ctx, r); return fail(RACC_HIP_ERR_DEVICE, "refit_create", e); }
+    if (wide) if (int rc = refitWideAttach(r)) { racc_hip_refit_destroy(ctx, r); return rc; }
     *out = r;
     return RACC_HIP_OK;
 } catch (const std::bad_alloc&) {      // (the host-side tables; the handle itself is allocated after them)
     return fail(RACC_HIP_ERR_NOMEM, "refit_create: out of host memory");
+}
+
+}  // namespace
+
+extern "C" {
+
+int racc_hip_refit_create(racc_hip_ctx* ctx, racc_hip_scene* scene, const uint32_t* indices, uint32_t index_count, uint32_t vertex_count,
+                          racc_hip_refit** out) {
+    return refitCreate(ctx, scene, indices, index_count, vertex_count, false, out);
 }
 
 int racc_hip_scene_refit_device(racc_hip_ctx* ctx, racc_hip_refit* r, const void* d_vertices, uint32_t vertex_count, void* stream) {
@@ -241,6 +270,13 @@ int racc_hip_scene_refit(racc_hip_ctx* ctx, racc_hip_refit* r, const float* vert
     if (vertex_count != r->vertexCount) return fail(RACC_HIP_ERR_INVALID, "scene_refit: vertex_count differs from the one the refit handle was created with");
     for (size_t i = 0; i < size_t(vertex_count); ++i)
         if (!std::isfinite(vertices[i * 4]) || !std::isfinite(vertices[i * 4 + 1]) || !std::isfinite(vertices[i * 4 + 2])) return fail(RACC_HIP_ERR_INVALID, "scene_refit: a vertex coordinate is not finite");
+    if (r->wideCount && r->scene->nodesWideQ && vertex_count) {      // no frame of the compressed copy is wider than the mesh: nothing is disabled below
+        for (int ax = 0; ax < 3; ++ax) {
+            float mn = vertices[ax], mx = mn;
+            for (size_t i = 1; i < size_t(vertex_count); ++i) { const float v = vertices[i * 4 + ax]; mn = v < mn ? v : mn; mx = v > mx ? v : mx; }
+            if (!std::isfinite(mx - mn)) return fail(RACC_HIP_ERR_LIMIT, "scene_refit: the vertices' extent on an axis overflows binary32 (the compressed 4-wide format cannot hold such a frame)");
+        }
+    }
     if (int rc = racc_hip_synchronize(ctx)) return rc;      // no traversal kernel (a chain's included) is alive while the records change
     const size_t bytes = size_t(vertex_count ? vertex_count : 1u) * 16;
     if (!r->vertices) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&r->vertices), bytes), "hipMalloc(refit vertices)");

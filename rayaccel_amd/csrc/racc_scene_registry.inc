@@ -15,6 +15,7 @@ struct RefitTopology { std::vector<uint32_t> words; uint32_t nodeCount = 0; };  
 struct SceneRecord {
     const racc_hip_ctx* owner;
     std::shared_ptr<const RefitTopology> topology;      // may be null
+    bool wideRefit = false;                             // a racc_hip_refit_create_wide handle exists (at most one per scene)
 };
 
 std::mutex g_sceneMutex;
@@ -31,6 +32,21 @@ const racc_hip_ctx* sceneOwner(const racc_hip_scene* scene) {
     std::lock_guard<std::mutex> g(g_sceneMutex);
     const auto it = g_scenes.find(scene);
     return it == g_scenes.end() ? nullptr : it->second.owner;
+}
+
+// the one wide refit handle a scene may have: false when the scene has no record or the handle is already out; the release is the handle's destroy
+bool sceneClaimWideRefit(const racc_hip_scene* scene) {
+    std::lock_guard<std::mutex> g(g_sceneMutex);
+    const auto it = g_scenes.find(scene);
+    if (it == g_scenes.end() || it->second.wideRefit) return false;
+    it->second.wideRefit = true;
+    return true;
+}
+
+void sceneReleaseWideRefit(const racc_hip_scene* scene) {
+    std::lock_guard<std::mutex> g(g_sceneMutex);
+    const auto it = g_scenes.find(scene);
+    if (it != g_scenes.end()) it->second.wideRefit = false;
 }
 
 }  // namespace

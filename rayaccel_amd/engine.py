@@ -95,6 +95,9 @@ ABI = {
     "racc_hip_scene_refit": (_i, [_vp, _vp, _vp, _u32]),
     "racc_hip_scene_refit_device": (_i, [_vp, _vp, _vp, _u32, _vp]),
     "racc_hip_refit_download": (_i, [_vp, _vp, _vp, _u32, _vp, _u32]),
+    "racc_hip_refit_create_wide": (_i, [_vp, _vp, _vp, _u32, _u32, _P(_vp)]),
+    "racc_hip_refit_download_wide": (_i, [_vp, _vp, _i, _vp, _u32, _P(_u32)]),
+    "racc_hip_refit_check": (_i, [_vp, _vp, _P(_u32)]),
     "racc_hip_world_create": (_i, [_vp, _vp, _P(_vp), _u32, _P(_vp)]),
     "racc_hip_world_update": (_i, [_vp, _vp, _vp, _u32]),
     "racc_hip_world_destroy": (_i, [_vp, _vp]),
@@ -146,6 +149,7 @@ ABI = {
     "racc_host_world_refit": (_i, [_vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _P(C.c_float), _vp]),
     "racc_host_scene_device_nodes": (_i, [_vp, _u32, _u32, _u32, _i, _vp, _u32, _P(_u32)]),
     "racc_host_scene_wide_nodes": (_i, [_vp, _u32, _u32, _u32, _i, _vp, _u32, _P(_u32), _P(_u32)]),
+    "racc_host_scene_wide_nodes_refit": (_i, [_vp, _vp, _u32, _u32, _u32, _i, _vp, _u32, _P(_u32), _P(_u32)]),
 }
 
 _lib = None
@@ -302,6 +306,22 @@ def wide_nodes(nodes, pair_count, remap_count, format=45):
     out = np.zeros((n.value, 32 if int(format) == 45 else 16), np.uint32)
     _check(lib.racc_host_scene_wide_nodes(*args, _ptr(out), n.value, C.byref(n), C.byref(bound)))
     return out, bound.value
+
+
+def host_wide_refit(built_nodes, now_nodes, pair_count, remap_count, format=45):
+    """racc_host_scene_wide_nodes_refit: the 4-wide records of a refitted scene (no GPU needed).  `built_nodes` = the node blob the scene
+    was uploaded from (it decides the collapse), `now_nodes` = the same topology with refitted boxes (host_refit(...)["nodes"], which
+    supplies every plane); pair_count / remap_count as wide_nodes takes them.  Returns (records laid out as wide_nodes' are, the number
+    of compressed frames that had to be disabled)."""
+    lib = load_library()
+    built, now = np.ascontiguousarray(built_nodes), np.ascontiguousarray(now_nodes)
+    assert built.dtype.itemsize == 64 and now.dtype.itemsize == 64 and len(built) == len(now)
+    n, disabled = C.c_uint32(0), C.c_uint32(0)
+    args = (_ptr(built), _ptr(now), len(built), pair_count, remap_count, int(format))
+    _check(lib.racc_host_scene_wide_nodes_refit(*args, None, 0, C.byref(n), C.byref(disabled)))
+    out = np.zeros((n.value, 32 if int(format) == 45 else 16), np.uint32)
+    _check(lib.racc_host_scene_wide_nodes_refit(*args, _ptr(out), n.value, C.byref(n), C.byref(disabled)))
+    return out, disabled.value
 
 
 def host_refit(blobs, vertices, indices):
@@ -503,6 +523,22 @@ class Refit:
         _check(load_library().racc_hip_refit_download(self._ctx._h, self._h, _ptr(nodes), len(nodes), _ptr(pairs), len(pairs)))
         return nodes, pairs
 
+    def download_wide(self, format):
+        """The scene's current 4-wide records of `format` (45: [N, 32] uint32 words, 50: [N, 16]), laid out as wide_nodes' are
+        (racc_hip_refit_download_wide); the scene must carry that copy."""
+        lib = load_library()
+        n = C.c_uint32(0)
+        _check(lib.racc_hip_refit_download_wide(self._ctx._h, self._h, int(format), None, 0, C.byref(n)))
+        out = np.zeros((n.value, 32 if int(format) == 45 else 16), np.uint32)
+        _check(lib.racc_hip_refit_download_wide(self._ctx._h, self._h, int(format), _ptr(out), n.value, C.byref(n)))
+        return out
+
+    def check(self):
+        """How many compressed frames the last refit disabled (racc_hip_refit_check; 0 on a plain handle); synchronise the refit's stream first."""
+        n = C.c_uint32(0)
+        _check(load_library().racc_hip_refit_check(self._ctx._h, self._h, C.byref(n)))
+        return int(n.value)
+
     def destroy(self):
         if self._h:
             load_library().racc_hip_refit_destroy(self._ctx._h, self._h)
@@ -615,11 +651,14 @@ class Context:
         hs = HostScene(vertices, indices, quality=None)
         return self.upload_scene(hs.nodes, hs.pairs, hs.remap)
 
-    def create_refit(self, scene, indices, vertex_count):
-        """racc_hip_refit_create: `indices` as the scene was built from, `vertex_count` = the length of every vertex array to come."""
+    def create_refit(self, scene, indices, vertex_count, wide=False):
+        """racc_hip_refit_create: `indices` as the scene was built from, `vertex_count` = the length of every vertex array to come.
+        wide=True: racc_hip_refit_create_wide, for a scene with a 4-wide and / or compressed copy (kernel_variant 45-53, wide_below):
+        every refit rewrites those copies too."""
         idx = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
         h = C.c_void_p()
-        _check(load_library().racc_hip_refit_create(self._h, scene._h, _ptr(idx), idx.size, int(vertex_count), C.byref(h)))
+        create = load_library().racc_hip_refit_create_wide if wide else load_library().racc_hip_refit_create
+        _check(create(self._h, scene._h, _ptr(idx), idx.size, int(vertex_count), C.byref(h)))
         return Refit(self, scene, h, vertex_count)
 
     def create_world(self, instances):
