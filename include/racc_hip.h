@@ -410,7 +410,8 @@ int racc_hip_world_occluded(racc_hip_ctx*, const racc_hip_world*, const void* ra
  * recomputed by the rule of racc_host_world_refit (below, "host world refit"), bit for bit.  A refitted world traces the moved instances
  * correctly — every result is what a world created with the new transforms reports; how FAST it traces them depends on how far the
  * instances moved from where the top level was built: its quality degrades (boxes of one subtree grow and overlap; instances that swap
- * places are the worst case).  racc_hip_world_update rebuilds the top level — "refit per frame, rebuild every N frames".
+ * places are the worst case).  racc_hip_world_rebuild_device (next section) rebuilds the top level on the same stream, racc_hip_world_update
+ * on the host — "refit per frame, rebuild every N frames".
  *
  * All refit state lives in the racc_hip_world_refit handle (device memory: 8 B per instance plus 36 B): per `order` position the slot
  * (2 * device record + side) its box goes to, every top-level record's own slot in its parent, one arrival counter per record, a 64-bit
@@ -437,7 +438,7 @@ int racc_hip_world_occluded(racc_hip_ctx*, const racc_hip_world*, const void* ra
  * blob layout (node_capacity in records, at least node_count of racc_hip_world_info; kind and parent are written as 0 and are
  * unspecified: the device does not hold them), order [count] and the current ray_pad.  Any output pointer may be NULL.  Blocking; the
  * caller has waited for whatever writes the world.
- * Out of scope: a device-side rebuild of the top level, device groups, the racc:: C++ interface, instance masks. */
+ * Out of scope: device groups, the racc:: C++ interface, instance masks.  (The rebuild of the top level on the device is the next section.) */
 struct racc_hip_world_refit;      /* the handle; no typedef, because racc_hip_world_refit is also the name of the blocking entry: write `struct racc_hip_world_refit*` */
 int racc_hip_world_refit_create(racc_hip_ctx*, racc_hip_world*, struct racc_hip_world_refit** out);
 int racc_hip_world_refit_destroy(racc_hip_ctx*, struct racc_hip_world_refit*);
@@ -446,6 +447,42 @@ int racc_hip_world_refit(racc_hip_ctx*, struct racc_hip_world_refit*, const floa
 int racc_hip_world_refit_check(racc_hip_ctx*, struct racc_hip_world_refit*, uint32_t* disabled_instances);
 int racc_hip_world_download(racc_hip_ctx*, const racc_hip_world*, float* inv12_out, void* nodes64_out, uint32_t node_capacity,
                             uint32_t* order_out, float* ray_pad_out);
+
+/* ---- instancing: rebuild of a world's top level on the device, in stream order ----
+ * ≙ nothing in the reference; every GPU API's top-level build is the usual counterpart.  What racc_hip_world_update does on the host —
+ * a new top-level tree for instances that changed neighbourhoods, where a refit's kept topology traces slowly — without leaving the
+ * stream: an LBVH (Morton codes of the instance box centres, a radix sort, Karras's 2012 hierarchy) written into the world's existing
+ * allocations.  The rule is stated once, in rayaccel_amd/csrc/racc_world_rebuild_rule.h; racc_host_world_rebuild (below, "host world
+ * rebuild") is its specification, and after a device rebuild racc_hip_world_download returns that function's inv, nodes (first, last, the
+ * four boxes), order and ray_pad byte for byte.  A rebuilt world answers every ray exactly as racc_hip_world_create with the same
+ * transforms does: the world contract (smallest t, ties to the lowest instance index) does not depend on the topology.  "Refit per frame,
+ * rebuild every N frames" — both on one handle and one stream.
+ *
+ * racc_hip_world_rebuild_create: racc_hip_world_refit_create plus the rebuild's scratch.  The handle is an ordinary world refit handle:
+ * every racc_hip_world_refit* entry works on it, it is the world's one handle, racc_hip_world_refit_destroy destroys it.  Device memory,
+ * beyond the plain handle's 8 B per instance plus 36 B: 32 B per instance (a 16-byte centre record and two 8-byte keys, formed and
+ * sorted) plus 32 B of words (centre bounds, height) plus the radix sort's temporary storage, sized at creation by rocPRIM for `count`
+ * 64-bit keys (another buffer of keys and its histograms: about 8 B per instance).
+ *   Stack room: the host cannot know the height of a tree built on the device without leaving the stream.  So at creation, and for as
+ * long as the handle lives, the world's info.height and info.spill_levels are raised to the rule's bound — 31 + ceil(log2(count)) levels,
+ * at most count - 1 (racc_world_rebuild_rule.h derives it) — keeping at least their current value: a launch issued after a device rebuild
+ * always has stack room.  racc_hip_world_update on such a world keeps the raised values.  racc_hip_world_refit_destroy, which
+ * synchronises the device, reads the real height back and sets info.height / spill_levels from it.
+ * racc_hip_world_rebuild_device: the arguments, alignment, ordering contract and disable rule of racc_hip_world_refit_device — `count`
+ * (= the world's) device-resident 3x4 transforms, 16-byte aligned, asynchronous on `stream`, not validated on the host; the member
+ * scenes' root boxes are read from their device records.  An instance the host rule would refuse is DISABLED as a refit disables it (NaN
+ * inv, neutral box, not in ray_pad, counted); it sorts behind every enabled instance and remains a leaf of the tree.
+ * RACC_HIP_ERR_INVALID on a handle racc_hip_world_refit_create made, before anything is enqueued.
+ * racc_hip_world_rebuild: host transforms, validated with the host rule (whatever racc_host_world_prepare refuses is refused, and the
+ * world is left as it was); calls racc_hip_synchronize(ctx), copies, runs on the handle's own stream and has completed on return.
+ * racc_hip_world_rebuild_check: the height (levels of top-level records on the longest root path) of the tree the world holds now and
+ * the disabled instances of the last refit or rebuild; the caller has synchronised the stream first.
+ * Out of scope: treelet or SAH optimisation of the LBVH, device groups, the racc:: C++ interface, instance masks, multi-level
+ * instancing, the 4-wide formats. */
+int racc_hip_world_rebuild_create(racc_hip_ctx*, racc_hip_world*, struct racc_hip_world_refit** out);
+int racc_hip_world_rebuild_device(racc_hip_ctx*, struct racc_hip_world_refit*, const void* d_transforms12, uint32_t count, void* stream);
+int racc_hip_world_rebuild(racc_hip_ctx*, struct racc_hip_world_refit*, const float* transforms12, uint32_t count);
+int racc_hip_world_rebuild_check(racc_hip_ctx*, struct racc_hip_world_refit*, uint32_t* height, uint32_t* disabled_instances);
 
 int racc_hip_get_launch_info(racc_hip_ctx* ctx, uint32_t lane, racc_hip_launch_info* info);
 /* With racc_hip_options::time_kernels: durations (ms, HIP events on the stream each launch went to) of the lane's traversal
@@ -635,6 +672,27 @@ int racc_host_world_prepare(const float* transforms12, const float* root_boxes6,
 int racc_host_world_refit(const float* transforms12, const float* root_boxes6, uint32_t count,
                           const void* nodes64, uint32_t node_count, const uint32_t* order,
                           float* inv12_out, float* world_boxes6_out, float* ray_pad_out, void* nodes64_out);
+
+/* Host world rebuild: the specification of racc_hip_world_rebuild* (pure function: no GPU, no handle).  The arguments and refusals of
+ * racc_host_world_prepare, whose inv12_out, world_boxes6_out and *ray_pad_out it reproduces as bytes; the tree is the LBVH of
+ * rayaccel_amd/csrc/racc_world_rebuild_rule.h instead of the median split:
+ *   centre     per axis float(0.5 * min + 0.5 * max) of the world box, evaluated in double
+ *   field      per axis floor(1024 (c - lo) / (hi - lo)) in double, at most 1023, 0 where hi == lo (lo / hi = the smallest / largest
+ *              centre); the three 10-bit values interleaved into 30 bits, x highest
+ *   key        (uint64(field) << 32) | instance index — unique; order_out[p] = the low word of the p-th smallest key
+ *   nodes64_out  node 0 the root over the positions [0, count - 1]; a node over [a, b] splits behind the last position that has a 0 in
+ *              the highest bit in which key[a] and key[b] differ; first child = the lower range; a child of one position p is the leaf
+ *              p | 1 << 24, a wider first child is node `split`, a wider last child node `split + 1` (0x80000000 | node); kind = 1,
+ *              parent = the parent's index (0xFFFFFFFF for the root); max(count - 1, 1) nodes, a world of one instance as
+ *              racc_host_world_prepare makes it.  Boxes: exactly racc_host_world_refit's fold over this topology, so refitting the
+ *              output to its own transforms reproduces it, signs of zeros included.
+ *   height_out   levels of nodes on the longest root path: at most 30 + ceil(log2(count)) and at most count - 1 (a node's split bit is
+ *              below its parent's; 30 field bits and ceil(log2(count)) index bits can differ).
+ * Deterministic.  RACC_HIP_ERR_INVALID before any output byte is written, as racc_host_world_prepare; the message names this entry. */
+int racc_host_world_rebuild(const float* transforms12, const float* root_boxes6, uint32_t count,
+                            float* inv12_out, float* world_boxes6_out, float* ray_pad_out,
+                            void* nodes64_out, uint32_t node_capacity, uint32_t* node_count_out,
+                            uint32_t* order_out, uint32_t* height_out);
 
 /* The device layout racc_hip_scene_upload gives the node blob (for tools and tests; needs no GPU).  Device record, 64 B: words 0-1 =
  * the two child references (re-numbered), words 2-3 unused, then the child boxes as six (min, max) plane pairs: Lx Ly Lz Rx Ry Rz.

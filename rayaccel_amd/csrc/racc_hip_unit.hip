@@ -16,4 +16,6 @@
 #include "racc_world_occlusion.inc"
 #include "racc_world_rule.h"
 #include "racc_world_refit.inc"
+#include "racc_world_rebuild_rule.h"
+#include "racc_world_rebuild.inc"
 #include "racc_wide_format.inc"

@@ -272,6 +272,9 @@ namespace {
 
 // racc_world_refit.inc: the handle's tables rebuilt from a new top level (`dev` = its device records on the host) and its pad word set.
 int worldRefitRebuild(racc_hip_world* w, const uint32_t* dev, float rayPad);
+// racc_world_rebuild.inc: while the world's handle can rebuild on the device, info.height / spill_levels are held at the LBVH's bound
+// and the handle's height word follows a host rebuild.  A no-op for any other world.
+int worldRebuildHold(racc_hip_world* w);
 
 // The member scenes' root boxes [count][6], read from the device: record 0's two child boxes combined.
 int worldRootBoxes(const racc_hip_world* w, std::vector<float>& rootBoxes) {
@@ -325,7 +328,10 @@ int worldCommit(racc_hip_world* w, const float* transforms12) try {
     w->info.node_count = nodeCount;
     w->info.height = height;
     w->info.spill_levels = height + 1u > uint32_t(kWorldTopLds) ? height + 1u - uint32_t(kWorldTopLds) : 0u;
-    if (w->refit) return worldRefitRebuild(w, dev.data(), rayPad);      // a live refit handle follows the new topology and pad
+    if (w->refit) {      // a live refit handle follows the new topology and pad
+        if (int rc = worldRefitRebuild(w, dev.data(), rayPad)) return rc;
+        return worldRebuildHold(w);
+    }
     return RACC_HIP_OK;
 } catch (const std::bad_alloc&) {
     return fail(RACC_HIP_ERR_NOMEM, "world: out of host memory");

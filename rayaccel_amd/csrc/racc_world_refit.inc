@@ -30,6 +30,12 @@ struct racc_hip_world_refit {
     float* rayPad = nullptr;                  // the device word the world kernels read
     float* transforms = nullptr;              // staging of the blocking entry, allocated at its first call
     hipStream_t stream = nullptr;             // ... and its stream
+    // the scratch of the device rebuild (racc_world_rebuild.inc): all NULL on a handle racc_hip_world_refit_create made
+    float4* centres = nullptr;                // [count] per instance: its box centre, w != 0 for a disabled instance
+    unsigned long long* keys = nullptr;       // [2][count]: as formed, then sorted
+    void* sortTemp = nullptr;                 // the radix sort's temporary storage, sized at creation ...
+    size_t sortTempBytes = 0;                 // ... to this
+    uint32_t* rebuildWords = nullptr;         // {centre bounds lo[3], hi[3] as ordered integers; height; unused}
 };
 
 namespace {
@@ -40,6 +46,10 @@ constexpr int kWorldRefitBlock = 256;
 __device__ __forceinline__ uint32_t* worldRefitDisabled(unsigned long long* state) { return reinterpret_cast<uint32_t*>(state + 1); }
 __device__ __forceinline__ uint32_t* worldRefitCounters(unsigned long long* state) { return reinterpret_cast<uint32_t*>(state + 2); }
 size_t worldRefitStateBytes(uint32_t capacity) { return 16 + size_t(capacity) * 4; }
+
+// racc_world_rebuild.inc: frees the rebuild's scratch; at destroy, the real height read back into the world's info.
+void worldRebuildFree(struct racc_hip_world_refit* r);
+void worldRebuildLeave(struct racc_hip_world_refit* r);
 
 __global__ void __launch_bounds__(kWorldRefitBlock) worldRefitKernel(const float* __restrict__ transforms, const WorldInstDev* __restrict__ table,
                                                                      const uint32_t* __restrict__ order, const uint32_t* __restrict__ slots, uint32_t count,
@@ -170,6 +180,7 @@ void worldRefitFree(WorldRefit* r) {
     if (r->state) hipFree(r->state);
     if (r->rayPad) hipFree(r->rayPad);
     if (r->transforms) hipFree(r->transforms);
+    worldRebuildFree(r);
     delete r;
 }
 
@@ -217,6 +228,7 @@ int racc_hip_world_refit_destroy(racc_hip_ctx* ctx, WorldRefit* r) {
     hipDeviceSynchronize();      // no refit and no world launch is alive while the pad moves back into the world
     float pad = w->rayPad;
     if (hipMemcpy(&pad, r->rayPad, 4, hipMemcpyDeviceToHost) == hipSuccess) w->rayPad = pad;
+    worldRebuildLeave(r);
     w->rayPadDev = nullptr;
     w->refit = nullptr;
     worldRefitFree(r);

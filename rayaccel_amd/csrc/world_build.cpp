@@ -19,8 +19,12 @@
 // Top level: BVH2 in the scenes' 64-byte node format (Scene.cpp:73-78), one instance per leaf, leaf reference = position in `order` |
 // 1 << 24.  Median split of the box centres along the longest axis of their bounds, ties by instance index: deterministic.  A world of
 // one instance has a root whose last child is the empty reference 0 (count 0; the kernel never enters it).
+//
+// racc_host_world_rebuild builds the other top level: the LBVH of racc_world_rebuild_rule.h over the same inverses and world boxes — the
+// specification of the rebuild on the device (racc_world_rebuild.inc), written top-down where the device searches per node.
 #include "racc_hip.h"
 #include "racc_world_rule.h"
+#include "racc_world_rebuild_rule.h"
 
 #include <algorithm>
 #include <cmath>
@@ -40,6 +44,7 @@ static_assert(sizeof(Node64) == 64, "reference record size");
 
 const char* const kPrepare = "racc_host_world_prepare";
 const char* const kRefit = "racc_host_world_refit";
+const char* const kRebuild = "racc_host_world_rebuild";
 
 // `who` = the entry the message names
 int refuse(const char* who, int code, const char* what, long long at = -1) {
@@ -127,6 +132,42 @@ struct Builder {
         n.kind = uint32_t(axis) + 1u; n.parent = parent; n.first = l; n.last = r;
         std::memcpy(n.box, box, sizeof(box));
         return self;
+    }
+};
+
+// The hierarchy of racc_world_rebuild_rule.h (rule 6) over sorted keys, top-down: a range is split at the highest bit in which its two
+// ends differ.  Boxes on the way back up, by racc_host_world_refit's fold (rule 7).
+struct LbvhBuilder {
+    const float* boxes;                 // [count][6] min, max
+    const std::vector<uint64_t>& keys;  // sorted
+    std::vector<Node64>& nodes;         // max(count - 1, 1) records, numbered as the rule says
+    uint32_t height = 0;
+
+    // the reference of the child covering [a, b], built if it is a record
+    uint32_t child(uint32_t a, uint32_t b, uint32_t record, uint32_t parent, uint32_t depth, float* box) {
+        if (a == b) {
+            std::memcpy(box, boxes + size_t(uint32_t(keys[a])) * 6, 24);
+            return (1u << 24) | a;
+        }
+        build(record, a, b, parent, depth);
+        const float* acc = nodes[record].box;      // the child's first-child box (accumulator), then its last-child box
+        const float* o = acc + 6;
+        for (int k = 0; k < 3; ++k) { box[k] = o[k] < acc[k] ? o[k] : acc[k]; box[3 + k] = o[3 + k] > acc[3 + k] ? o[3 + k] : acc[3 + k]; }
+        return 0x80000000u | record;
+    }
+
+    // record `self` over the positions [a, b], a < b
+    void build(uint32_t self, uint32_t a, uint32_t b, uint32_t parent, uint32_t depth) {
+        if (depth > height) height = depth;
+        const int bit = 63 - racc_world_rebuild_rule::commonPrefix(keys[a], keys[b]);
+        // every key of [a, b] agrees with both ends above `bit`, so the range is zeros then ones there: the last zero
+        const uint32_t s = uint32_t(std::partition_point(keys.begin() + a, keys.begin() + b + 1, [bit](uint64_t k) { return ((k >> bit) & 1u) == 0u; }) - keys.begin()) - 1u;
+        float box[12];
+        const uint32_t l = child(a, s, s, self, depth + 1, box);
+        const uint32_t r = child(s + 1u, b, s + 1u, self, depth + 1, box + 6);
+        Node64& n = nodes[self];
+        n.kind = 1u; n.parent = parent; n.first = l; n.last = r;
+        std::memcpy(n.box, box, sizeof(box));
     }
 };
 
@@ -258,4 +299,60 @@ extern "C" int racc_host_world_refit(const float* transforms12, const float* roo
     return RACC_HIP_OK;
 } catch (const std::bad_alloc&) {
     return refuse(kRefit, RACC_HIP_ERR_NOMEM, "out of host memory");
+}
+
+// The specification of racc_hip_world_rebuild* (racc_world_rebuild.inc): the top-level LBVH of racc_world_rebuild_rule.h.
+extern "C" int racc_host_world_rebuild(const float* transforms12, const float* root_boxes6, uint32_t count,
+                                       float* inv12_out, float* world_boxes6_out, float* ray_pad_out,
+                                       void* nodes64_out, uint32_t node_capacity, uint32_t* node_count_out,
+                                       uint32_t* order_out, uint32_t* height_out) try {
+    namespace rule = racc_world_rebuild_rule;
+    if (!transforms12 || !root_boxes6) return refuse(kRebuild, RACC_HIP_ERR_INVALID, "transforms / root boxes pointer is NULL");
+    if (!inv12_out || !world_boxes6_out || !ray_pad_out || !nodes64_out || !node_count_out || !order_out || !height_out) return refuse(kRebuild, RACC_HIP_ERR_INVALID, "an output pointer is NULL");
+    if (!count) return refuse(kRebuild, RACC_HIP_ERR_INVALID, "count is 0: a world has at least one instance");
+    if (count > RACC_HIP_WORLD_MAX_INSTANCES) return refuse(kRebuild, RACC_HIP_ERR_INVALID, "more than 2^20 instances");
+    const uint32_t nodesNeeded = count > 1u ? count - 1u : 1u;
+    if (node_capacity < nodesNeeded) return refuse(kRebuild, RACC_HIP_ERR_INVALID, "node_capacity is below max(count - 1, 1)");
+
+    // everything is validated and computed into buffers of our own before the first output byte is written
+    std::vector<float> inv(size_t(count) * 12), boxes(size_t(count) * 6);
+    float rayPad = 0.0f;
+    if (int rc = perInstance(kRebuild, transforms12, root_boxes6, count, inv.data(), boxes.data(), rayPad)) return rc;
+
+    std::vector<float> centre(size_t(count) * 3);
+    float lo[3], hi[3];
+    for (uint32_t i = 0; i < count; ++i)
+        for (int k = 0; k < 3; ++k) {
+            const float c = rule::centre(boxes[size_t(i) * 6 + k], boxes[size_t(i) * 6 + 3 + k]);
+            centre[size_t(i) * 3 + k] = c;
+            if (!i || c < lo[k]) lo[k] = c;
+            if (!i || c > hi[k]) hi[k] = c;
+        }
+    std::vector<uint64_t> keys(count);
+    for (uint32_t i = 0; i < count; ++i) keys[i] = rule::key(rule::field(&centre[size_t(i) * 3], lo, hi), i);
+    std::sort(keys.begin(), keys.end());
+
+    std::vector<Node64> nodes(nodesNeeded);
+    uint32_t height = 1;
+    if (count == 1u) {
+        Node64 n{};
+        n.kind = 1u; n.parent = 0xFFFFFFFFu; n.first = (1u << 24) | 0u; n.last = 0u;
+        std::memcpy(n.box, boxes.data(), 24);
+        nodes[0] = n;
+    } else {
+        LbvhBuilder bl{ boxes.data(), keys, nodes };
+        bl.build(0u, 0u, count - 1u, 0xFFFFFFFFu, 1u);
+        height = bl.height;
+    }
+
+    std::memcpy(inv12_out, inv.data(), inv.size() * sizeof(float));
+    std::memcpy(world_boxes6_out, boxes.data(), boxes.size() * sizeof(float));
+    *ray_pad_out = rayPad;
+    std::memcpy(nodes64_out, nodes.data(), nodes.size() * sizeof(Node64));
+    *node_count_out = nodesNeeded;
+    for (uint32_t p = 0; p < count; ++p) order_out[p] = uint32_t(keys[p]);
+    *height_out = height;
+    return RACC_HIP_OK;
+} catch (const std::bad_alloc&) {
+    return refuse(kRebuild, RACC_HIP_ERR_NOMEM, "out of host memory");
 }

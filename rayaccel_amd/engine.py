@@ -112,6 +112,10 @@ ABI = {
     "racc_hip_world_refit": (_i, [_vp, _vp, _vp, _u32]),
     "racc_hip_world_refit_check": (_i, [_vp, _vp, _P(_u32)]),
     "racc_hip_world_download": (_i, [_vp, _vp, _vp, _vp, _u32, _vp, _P(C.c_float)]),
+    "racc_hip_world_rebuild_create": (_i, [_vp, _vp, _P(_vp)]),
+    "racc_hip_world_rebuild_device": (_i, [_vp, _vp, _vp, _u32, _vp]),
+    "racc_hip_world_rebuild": (_i, [_vp, _vp, _vp, _u32]),
+    "racc_hip_world_rebuild_check": (_i, [_vp, _vp, _P(_u32), _P(_u32)]),
     "racc_hip_get_launch_info": (_i, [_vp, _u32, _P(LaunchInfo)]),
     "racc_hip_read_kernel_times": (_i, [_vp, _u32, _P(C.c_float), _u32, _P(_u32)]),
     "racc_hip_read_stats": (_i, [_vp, _u32, _P(_u64), _i]),
@@ -147,6 +151,7 @@ ABI = {
     "racc_host_blobs_refit": (_i, [_vp, _u32, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _vp]),
     "racc_host_world_prepare": (_i, [_vp, _vp, _u32, _vp, _vp, _P(C.c_float), _vp, _u32, _P(_u32), _vp, _P(_u32)]),
     "racc_host_world_refit": (_i, [_vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _P(C.c_float), _vp]),
+    "racc_host_world_rebuild": (_i, [_vp, _vp, _u32, _vp, _vp, _P(C.c_float), _vp, _u32, _P(_u32), _vp, _P(_u32)]),
     "racc_host_scene_device_nodes": (_i, [_vp, _u32, _u32, _u32, _i, _vp, _u32, _P(_u32)]),
     "racc_host_scene_wide_nodes": (_i, [_vp, _u32, _u32, _u32, _i, _vp, _u32, _P(_u32), _P(_u32)]),
     "racc_host_scene_wide_nodes_refit": (_i, [_vp, _vp, _u32, _u32, _u32, _i, _vp, _u32, _P(_u32), _P(_u32)]),
@@ -357,7 +362,7 @@ def root_box(nodes):
     return np.concatenate([np.minimum(n["leftMin"], n["rightMin"]), np.maximum(n["leftMax"], n["rightMax"])]).astype(np.float32)
 
 
-def host_world_prepare(transforms, root_boxes):
+def host_world_prepare(transforms, root_boxes, _entry="racc_host_world_prepare"):
     """racc_host_world_prepare: the host side of instancing (no GPU needed).  `transforms` [N,3,4] object-to-world, `root_boxes` [N,6]
     object-space {min, max} (root_box()).  Returns dict(inv [N,3,4], world_boxes [N,6], ray_pad, nodes (top-level BVH2, GPU_NODE_DTYPE),
     order [N], height)."""
@@ -370,9 +375,15 @@ def host_world_prepare(transforms, root_boxes):
     inv, boxes = np.zeros((n, 12), np.float32), np.zeros((n, 6), np.float32)
     nodes, order = np.zeros(cap, GPU_NODE_DTYPE), np.zeros(max(n, 1), np.uint32)
     pad, nn, height = C.c_float(0), C.c_uint32(0), C.c_uint32(0)
-    _check(load_library().racc_host_world_prepare(_ptr(t), _ptr(rb), n, _ptr(inv), _ptr(boxes), C.byref(pad), _ptr(nodes), cap, C.byref(nn),
-                                                  _ptr(order), C.byref(height)))
+    _check(getattr(load_library(), _entry)(_ptr(t), _ptr(rb), n, _ptr(inv), _ptr(boxes), C.byref(pad), _ptr(nodes), cap, C.byref(nn),
+                                           _ptr(order), C.byref(height)))
     return dict(inv=inv.reshape(n, 3, 4), world_boxes=boxes, ray_pad=float(pad.value), nodes=nodes[:nn.value].copy(), order=order[:n], height=int(height.value))
+
+
+def host_world_rebuild(transforms, root_boxes):
+    """racc_host_world_rebuild: the specification of the device rebuild (no GPU needed) — host_world_prepare's arguments and result, with
+    the top-level LBVH of racc_world_rebuild_rule.h (Morton keys of the box centres, Karras's hierarchy) in place of the median split."""
+    return host_world_prepare(transforms, root_boxes, _entry="racc_host_world_rebuild")
 
 
 def host_world_refit(transforms, root_boxes, nodes, order):
@@ -419,6 +430,25 @@ class WorldRefit:
         n = C.c_uint32(0)
         _check(load_library().racc_hip_world_refit_check(self._ctx._h, self._h, C.byref(n)))
         return int(n.value)
+
+    def rebuild(self, transforms):
+        """Host transforms [N,3,4], validated, blocking (racc_hip_world_rebuild): a new top-level tree, built on the device.  Needs a handle
+        of World.create_refit(rebuild=True)."""
+        t = _as_transforms(transforms)
+        _check(load_library().racc_hip_world_rebuild(self._ctx._h, self._h, _ptr(t), len(t)))
+
+    def rebuild_device(self, d_transforms, stream=None):
+        """Device-resident transforms as refit_device takes them, asynchronous on `stream` (racc_hip_world_rebuild_device): the top level
+        rebuilt on the device — for instances that changed neighbourhoods, where a refit's kept topology traces slowly.  Launches on the
+        world issued later on the same stream need no wait."""
+        _check(load_library().racc_hip_world_rebuild_device(self._ctx._h, self._h, d_transforms, self._world.count, stream))
+
+    def check_rebuild(self):
+        """(height of the tree the world holds now, instances the last refit or rebuild disabled) (racc_hip_world_rebuild_check);
+        synchronise the stream first."""
+        height, n = C.c_uint32(0), C.c_uint32(0)
+        _check(load_library().racc_hip_world_rebuild_check(self._ctx._h, self._h, C.byref(height), C.byref(n)))
+        return int(height.value), int(n.value)
 
     def destroy(self):
         if self._h:
@@ -479,10 +509,13 @@ class World:
         t = _as_transforms(transforms)
         _check(load_library().racc_hip_world_update(self._ctx._h, self._h, _ptr(t), len(t)))
 
-    def create_refit(self):
-        """racc_hip_world_refit_create: the handle that refits this world's top level on the device (at most one per world)."""
+    def create_refit(self, rebuild=False):
+        """racc_hip_world_refit_create: the handle that refits this world's top level on the device (at most one per world).  With
+        rebuild=True, racc_hip_world_rebuild_create: the same handle with the scratch to rebuild the top level on the device as well; the
+        world's info.height / spill_levels then hold the LBVH's bound while it lives."""
         h = C.c_void_p()
-        _check(load_library().racc_hip_world_refit_create(self._ctx._h, self._h, C.byref(h)))
+        lib = load_library()
+        _check((lib.racc_hip_world_rebuild_create if rebuild else lib.racc_hip_world_refit_create)(self._ctx._h, self._h, C.byref(h)))
         return WorldRefit(self, h)
 
     def download(self):
