@@ -273,7 +273,8 @@ int racc_hip_occluded(racc_hip_ctx*, const racc_hip_scene*, const void* rays, ui
 
 /* ---- dynamic scenes: refit of a device-resident scene to moved vertices ----
  * ≙ nothing in the reference (its scenes are frozen at createScene, Scene.cpp:216-349); Embree's rtcCommitScene on a deformable scene and
- * every GPU API's BVH update are the usual counterparts.  The topology stays (child references, leaf ranges, remap, the device node order,
+ * every GPU API's BVH update are the usual counterparts — and their bottom-level BUILD is "dynamic scenes: build and rebuild of a
+ * scene's tree on the device" below, for a mesh that has left what a kept topology can bear.  The topology stays (child references, leaf ranges, remap, the device node order,
  * hence inner_height, max_leaf_pairs and every count in racc_hip_scene_info); the 48 B pair records and the child boxes of the 64 B node
  * records are recomputed by the rule of racc_host_blobs_refit (below, "host refit"), bit for bit.  A refitted tree traces the moved mesh
  * correctly; how well it traces it depends on how far the vertices moved from the positions the tree was built for.
@@ -328,6 +329,63 @@ int racc_hip_refit_download(racc_hip_ctx*, racc_hip_refit*, void* nodes64_out, u
 int racc_hip_refit_create_wide(racc_hip_ctx*, racc_hip_scene*, const uint32_t* indices, uint32_t index_count, uint32_t vertex_count, racc_hip_refit** out);
 int racc_hip_refit_download_wide(racc_hip_ctx*, racc_hip_refit*, int format, void* out, uint32_t capacity, uint32_t* count);
 int racc_hip_refit_check(racc_hip_ctx*, racc_hip_refit*, uint32_t* disabled_frames);
+
+/* ---- dynamic scenes: build and rebuild of a scene's tree on the device, in stream order ----
+ * ≙ nothing in the reference; every GPU API's bottom-level build is the usual counterpart.  What racc_host_scene_build plus
+ * racc_hip_scene_upload do on the host — a new tree for a mesh that deformed beyond what a refit's kept topology can bear, or for
+ * vertices that come from a kernel — without leaving the stream: an LBVH over the triangles (Morton codes of the triangle box centres, a
+ * radix sort, Karras's 2012 hierarchy), one triangle per pair and one pair per leaf, written into the scene's existing allocations in the
+ * formats every kernel reads.  The rule is stated once, in rayaccel_amd/csrc/racc_scene_rebuild_rule.h; racc_host_scene_rebuild (below,
+ * "host scene rebuild") is its specification, and after a device rebuild racc_hip_refit_download plus the scene's remap are that
+ * function's nodes, pairs and remap byte for byte.  "Refit per frame, rebuild every N frames" — both on one handle and one stream.
+ * Such a tree is expected to trace well below racc_host_scene_build's SAH tree (lone triangles, no line-paired record order, no
+ * surface-area heuristic): DESIGN.md §3 has the measured ratio, which is what tells a caller how often a host build is worth its price.
+ *
+ * racc_hip_scene_rebuild_create (blocking): runs racc_host_scene_rebuild on the given xyzw vertices (its refusals, under its name),
+ * uploads the blobs through racc_hip_scene_upload — which does all allocation — makes a refit handle with the rebuild's scratch, and
+ * runs one device rebuild, so that the scene is in the rebuild's own layout from then on: device record = node index, the upload's
+ * padding records unreferenced behind the T - 1 nodes.  Device memory beyond a plain handle's: 12 B per triangle of indices, 24 B per
+ * triangle of keys and values (formed, sorted), 16 B per vertex of staging, 32 B of words (centre bounds, height) and rocPRIM's temporary
+ * storage, sized at creation.  The handle is an ordinary racc_hip_refit: racc_hip_scene_refit, racc_hip_scene_refit_device,
+ * racc_hip_refit_download (nodes in node order: the identity map), racc_hip_refit_check and racc_hip_refit_destroy work on it, and
+ * racc_hip_scene_get_info reports max_leaf_pairs = 1.  It is the scene's ONLY handle: the scene's registry record is flagged and its
+ * topology words are dropped, and racc_hip_refit_create / racc_hip_refit_create_wide refuse the scene from then on — a device rebuild
+ * changes the topology, the words a plain handle keeps would go stale and it would write wrong boxes.  Destroy the handle before the
+ * scene: racc_hip_scene_free returns RACC_HIP_ERR_INVALID while it lives.
+ * RACC_HIP_ERR_INVALID, nothing created: a context whose uploads carry a 4-wide, compressed or SoA copy of the tree or put the top of
+ * the tree first (kernel_variant 45-53, wide_below != 0, the SoA variant, 60-63) — a rebuild rewrites the binary records only, the copies
+ * and the cached top would go stale.
+ * racc_hip_scene_rebuild_device: device xyzw vertices, NOT validated — they must be finite; with vertices that are not the results are
+ * unspecified, but every access of the rebuild stays inside its arrays (the rule header says why) — asynchronous on `stream`, with the
+ * ordering contract of racc_hip_scene_refit_device.  RACC_HIP_ERR_INVALID before anything is enqueued: a handle racc_hip_refit_create*
+ * made, a vertex_count that differs from the handle's.
+ * racc_hip_scene_rebuild: host vertices, validated by the host rule (finite); calls racc_hip_synchronize(ctx) as racc_hip_scene_refit
+ * does, runs on the handle's stream and has completed on return.
+ * racc_hip_scene_rebuild_check: the height (levels of nodes on the longest root path) of the tree the scene holds now; the caller has
+ * synchronised the stream first.
+ *   Stack room: the host cannot know the height of a tree built on the device without leaving the stream.  So
+ * racc_hip_scene_rebuild_device raises the scene's info.inner_height (and info.spill_levels) to the rule's bound before it enqueues
+ * anything — 63 + ceil(log2 T) levels, at most T - 1 (the rule header derives it) — and every launch sizes its spill from
+ * info.inner_height: a launch issued behind a device rebuild always has stack room.  The price of the bound: up to 87 levels against the
+ * default kernel's 12 in LDS is up to 75 spilled levels x 4 B x 524,288 grid threads = 157 MB of spill area per lane, allocated at the
+ * first launch that needs it and kept.  racc_hip_scene_rebuild (blocking) and racc_hip_scene_rebuild_check set info.inner_height to the
+ * real height, and the next launch sizes its spill from that.  (info is read by launches and written by these entries: the ordering
+ * contract covers it.)
+ *   Worlds: racc_hip_world_create reads its scenes' inner_height once.  A world created after racc_hip_scene_rebuild_check or the
+ * blocking rebuild has stack room for the tree the scene holds THEN (create it anew after a rebuild that makes the tree taller); a world
+ * created between racc_hip_scene_rebuild_device and the check reads the bound and has room for every rebuild to come, at the bound's
+ * price.
+ * racc_hip_refit_download_remap: the scene's remap as the device holds it now (remap_count of racc_hip_scene_info words; any refit handle —
+ * only a rebuild changes it); the caller has waited for the rebuild.  With racc_hip_refit_download: the whole scene back as blobs.
+ * Out of scope: pairing of triangles that share an edge (every pair is a lone triangle), the 128-byte line order of the records, SAH or
+ * treelet optimisation of the LBVH, the 4-wide and compressed formats, device groups, the racc:: C++ interface, changing the triangle
+ * count on a live handle. */
+int racc_hip_scene_rebuild_create(racc_hip_ctx*, const float* vertices, uint32_t vertex_count, const uint32_t* indices, uint32_t index_count,
+                                  racc_hip_scene** scene_out, racc_hip_refit** out);
+int racc_hip_scene_rebuild_device(racc_hip_ctx*, racc_hip_refit*, const void* d_vertices, uint32_t vertex_count, void* stream);
+int racc_hip_scene_rebuild(racc_hip_ctx*, racc_hip_refit*, const float* vertices, uint32_t vertex_count);
+int racc_hip_scene_rebuild_check(racc_hip_ctx*, racc_hip_refit*, uint32_t* height);
+int racc_hip_refit_download_remap(racc_hip_ctx*, racc_hip_refit*, uint32_t* remap_out, uint32_t remap_capacity);
 
 /* ---- instancing: two-level scenes with per-instance transforms ----
  * ≙ nothing in the reference (one flattened scene per racc::Scene, Scene.cpp:216-349); Embree's RTC_GEOMETRY_TYPE_INSTANCE and the
@@ -630,6 +688,31 @@ int racc_host_blobs_refit(const void* nodes64, uint32_t node_count,
                           const float* vertices /* xyzw */, uint32_t vertex_count,
                           const uint32_t* indices, uint32_t index_count,
                           void* nodes64_out, void* pairs48_out);
+
+/* Host scene rebuild: the specification of racc_hip_scene_rebuild* (pure function: no GPU, no handle) — an LBVH over the triangles of a
+ * mesh in the reference's blob formats, by the rule of rayaccel_amd/csrc/racc_scene_rebuild_rule.h.  T = index_count / 3.
+ *   triangle box  the select of racc_host_blobs_refit folded over the triangle's three vertices in index order, from the first one
+ *   centre     per axis float(0.5 * min + 0.5 * max) of that box, evaluated in double
+ *   field      per axis floor(2^21 (c - lo) / (hi - lo)) in double, at most 2^21 - 1, 0 where hi > lo does not hold (lo / hi = the smallest
+ *              / largest centre); the three 21-bit values interleaved into 63 bits, x highest
+ *   key        the pair (field, triangle index), ordered lexicographically — unique; order[p] = the triangle of the p-th smallest key
+ *   pairs48_out  pair p is triangle order[p] alone: vertices a[0], a[1], a[2], a[1], the record as racc_host_blobs_refit packs it;
+ *              *pair_count_padded = the smallest multiple of 32 above T, the padding copies of pair 0
+ *   remap_out  remap[2p] = order[p], remap[2p + 1] = 0; *remap_count = 2T
+ *   nodes64_out  node 0 the root over the positions [0, T - 1]; a node over [a, b] splits behind the last position that has a 0 in the
+ *              highest bit in which key[a] and key[b] differ (of the 95-bit concatenation); first child = the lower range; a child of one
+ *              position p is the leaf p | 1 << 24, a wider first child is node `split`, a wider last child node `split + 1`
+ *              (0x80000000 | node); kind = 1, parent = the parent's index (0xFFFFFFFF for the root); *node_count = T - 1.  Boxes: exactly
+ *              racc_host_blobs_refit's fold over this topology, so refitting the output to its own vertices reproduces it, signs of
+ *              zeros included.
+ *   height     levels of nodes on the longest root path: at most 63 + ceil(log2 T) and at most T - 1.
+ * Deterministic.  Before any output byte is written: RACC_HIP_ERR_INVALID for a NULL pointer, index_count % 3 != 0, T < 2, an index >=
+ * vertex_count, a vertex coordinate (x, y, z) that is not finite, node_capacity < T - 1, pair_capacity < the padded pair count,
+ * remap_capacity < 2T; RACC_HIP_ERR_LIMIT for T >= 2^24. */
+int racc_host_scene_rebuild(const float* vertices /* xyzw */, uint32_t vertex_count, const uint32_t* indices, uint32_t index_count,
+                            void* nodes64_out, uint32_t node_capacity, uint32_t* node_count,
+                            void* pairs48_out, uint32_t pair_capacity, uint32_t* pair_count_padded,
+                            uint32_t* remap_out, uint32_t remap_capacity, uint32_t* remap_count, uint32_t* height);
 
 /* Host side of instancing (racc_hip_world_* above; pure function, no GPU, no handle) — ≙ nothing in the reference.  Inputs: `count`
  * 3x4 row-major object-to-world transforms and each instance's object-space root box {min[3], max[3]} (the union of the two child boxes

@@ -18,4 +18,6 @@
 #include "racc_world_refit.inc"
 #include "racc_world_rebuild_rule.h"
 #include "racc_world_rebuild.inc"
+#include "racc_scene_rebuild_rule.h"
+#include "racc_scene_rebuild.inc"
 #include "racc_wide_format.inc"

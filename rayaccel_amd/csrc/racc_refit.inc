@@ -101,6 +101,15 @@ struct racc_hip_refit {
     uint32_t wideCount = 0;                   // 0: a plain handle
     uint4* wideSources = nullptr;             // [wideCount] per slot 2 * device record + side of the binary child box it copies, kWideNone in an unused slot
     uint32_t* wideDisabled = nullptr;         // [1] compressed frames the last refit disabled (racc_hip_refit_check)
+    // a handle of racc_hip_scene_rebuild_create (racc_scene_rebuild.inc): no topology words, device record = node index, the tables above
+    // are written by the rebuild's kernels; parentSlot and counters hold max(deviceNodes, triangles) entries
+    uint32_t* rebuildWords = nullptr;         // [8] centre bounds lo[3], hi[3] as ordered integers, height, unused; null: not a rebuild handle
+    uint32_t triCount = 0;
+    uint32_t* rebuildIndices = nullptr;       // [3 * triCount] the mesh's index triples
+    unsigned long long* rebuildKeys = nullptr;      // [2 * triCount] Morton fields: as formed, sorted
+    uint32_t* rebuildValues = nullptr;        // [2 * triCount] triangle indices: as formed, sorted
+    void* sortTemp = nullptr;                 // rocPRIM's temporary storage, sized at creation
+    size_t sortTempBytes = 0;
 };
 
 namespace {
@@ -108,6 +117,8 @@ namespace {
 int refitWideLaunch(racc_hip_refit* r, hipStream_t st);      // racc_refit_wide.inc
 int refitWideAttach(racc_hip_refit* r);
 void refitWideDetach(racc_hip_refit* r);
+void sceneRebuildDetach(racc_hip_refit* r);      // racc_scene_rebuild.inc
+int sceneRebuildDownload(racc_hip_refit* r, void* nodes64_out, uint32_t node_capacity, void* pairs48_out, uint32_t pair_capacity);
 
 int refitLaunch(racc_hip_refit* r, const float4* dVertices, hipStream_t st) {
     const racc_hip_scene* s = r->scene;
@@ -137,6 +148,7 @@ int racc_hip_refit_destroy(racc_hip_ctx* ctx, racc_hip_refit* r) {
     if (r->counters) hipFree(r->counters);
     if (r->vertices) hipFree(r->vertices);
     refitWideDetach(r);
+    sceneRebuildDetach(r);
     delete r;
     return RACC_HIP_OK;
 }
@@ -152,6 +164,9 @@ int refitCreate(racc_hip_ctx* ctx, racc_hip_scene* scene, const uint32_t* indice
     if (!out) return fail(RACC_HIP_ERR_INVALID, "refit_create: out is NULL");
     *out = nullptr;
     if (!scene || !indices) return fail(RACC_HIP_ERR_INVALID, "refit_create: scene/indices is NULL");
+    if (sceneIsRebuilt(scene))
+        return fail(RACC_HIP_ERR_INVALID, "refit_create: the scene was made by racc_hip_scene_rebuild_create, whose handle is its only handle: a device rebuild changes the "
+                                          "topology, the words a plain handle keeps would go stale and it would write wrong boxes");
     if (!wide && (scene->nodesWide || scene->nodesWideQ || scene->nodesSoa))
         return fail(RACC_HIP_ERR_INVALID, "refit_create: the scene carries a 4-wide, compressed or SoA copy of the tree (kernel_variant 45 / 50, wide_below, the SoA variant); "
                                           "racc_hip_refit_create_wide refits the 4-wide and compressed copies, a stale copy would give wrong hits");
@@ -289,6 +304,7 @@ int racc_hip_scene_refit(racc_hip_ctx* ctx, racc_hip_refit* r, const float* vert
 int racc_hip_refit_download(racc_hip_ctx* ctx, racc_hip_refit* r, void* nodes64_out, uint32_t node_capacity, void* pairs48_out, uint32_t pair_capacity) {
     if (!ctx) return fail(RACC_HIP_ERR_INVALID, "refit_download: ctx is NULL");
     if (!r) return fail(RACC_HIP_ERR_INVALID, "refit_download: refit is NULL");
+    if (r->rebuildWords) { HIP_TRY(hipSetDevice(ctx->device), "hipSetDevice"); return sceneRebuildDownload(r, nodes64_out, node_capacity, pairs48_out, pair_capacity); }
     const racc_hip_scene* s = r->scene;
     const uint32_t nodeCount = r->topology->nodeCount;
     if ((nodes64_out && node_capacity < nodeCount) || (pairs48_out && pair_capacity < s->info.pair_count)) return fail(RACC_HIP_ERR_INVALID, "refit_download: capacity too small");

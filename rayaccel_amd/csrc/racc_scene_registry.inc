@@ -16,6 +16,10 @@ struct SceneRecord {
     const racc_hip_ctx* owner;
     std::shared_ptr<const RefitTopology> topology;      // may be null
     bool wideRefit = false;                             // a racc_hip_refit_create_wide handle exists (at most one per scene)
+    // racc_hip_scene_rebuild_create made this scene (racc_scene_rebuild.inc): its records are in the rebuild's own layout, the topology words
+    // are dropped for good (a device rebuild would make them stale) and the rebuild's handle is the scene's only handle ...
+    bool rebuilt = false;
+    bool rebuildLive = false;                           // ... which is alive: racc_hip_scene_free refuses
 };
 
 std::mutex g_sceneMutex;
@@ -49,6 +53,28 @@ void sceneReleaseWideRefit(const racc_hip_scene* scene) {
     if (it != g_scenes.end()) it->second.wideRefit = false;
 }
 
+// racc_hip_scene_rebuild_create: false for a scene without a record; the handle's destroy ends `rebuildLive`, `rebuilt` stays
+bool sceneClaimRebuild(const racc_hip_scene* scene) {
+    std::lock_guard<std::mutex> g(g_sceneMutex);
+    const auto it = g_scenes.find(scene);
+    if (it == g_scenes.end()) return false;
+    it->second.topology.reset();
+    it->second.rebuilt = it->second.rebuildLive = true;
+    return true;
+}
+
+void sceneReleaseRebuild(const racc_hip_scene* scene) {
+    std::lock_guard<std::mutex> g(g_sceneMutex);
+    const auto it = g_scenes.find(scene);
+    if (it != g_scenes.end()) it->second.rebuildLive = false;
+}
+
+bool sceneIsRebuilt(const racc_hip_scene* scene) {
+    std::lock_guard<std::mutex> g(g_sceneMutex);
+    const auto it = g_scenes.find(scene);
+    return it != g_scenes.end() && it->second.rebuilt;
+}
+
 }  // namespace
 
 extern "C" {
@@ -79,6 +105,9 @@ int racc_hip_scene_upload(racc_hip_ctx* ctx, const void* nodes64, uint32_t node_
 int racc_hip_scene_free(racc_hip_ctx* ctx, racc_hip_scene* scene) {
     if (scene) {
         std::lock_guard<std::mutex> g(g_sceneMutex);
+        const auto it = g_scenes.find(scene);
+        if (it != g_scenes.end() && it->second.rebuildLive)
+            return fail(RACC_HIP_ERR_INVALID, "scene_free: the scene has a rebuild handle (racc_hip_scene_rebuild_create): racc_hip_refit_destroy comes first");
         g_scenes.erase(scene);
     }
     return raccSceneFreeBase(ctx, scene);

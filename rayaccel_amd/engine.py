@@ -98,6 +98,11 @@ ABI = {
     "racc_hip_refit_create_wide": (_i, [_vp, _vp, _vp, _u32, _u32, _P(_vp)]),
     "racc_hip_refit_download_wide": (_i, [_vp, _vp, _i, _vp, _u32, _P(_u32)]),
     "racc_hip_refit_check": (_i, [_vp, _vp, _P(_u32)]),
+    "racc_hip_scene_rebuild_create": (_i, [_vp, _vp, _u32, _vp, _u32, _P(_vp), _P(_vp)]),
+    "racc_hip_scene_rebuild_device": (_i, [_vp, _vp, _vp, _u32, _vp]),
+    "racc_hip_scene_rebuild": (_i, [_vp, _vp, _vp, _u32]),
+    "racc_hip_scene_rebuild_check": (_i, [_vp, _vp, _P(_u32)]),
+    "racc_hip_refit_download_remap": (_i, [_vp, _vp, _vp, _u32]),
     "racc_hip_world_create": (_i, [_vp, _vp, _P(_vp), _u32, _P(_vp)]),
     "racc_hip_world_update": (_i, [_vp, _vp, _vp, _u32]),
     "racc_hip_world_destroy": (_i, [_vp, _vp]),
@@ -149,6 +154,7 @@ ABI = {
     "racc_host_scene_blobs": (_i, [_vp, _P(_vp), _P(_u32), _P(_vp), _P(_u32), _P(_u32), _P(_vp), _P(_u32)]),
     "racc_host_scene_bvh2": (_i, [_vp, _P(_vp), _P(_u32), _P(_vp), _P(_u32)]),
     "racc_host_blobs_refit": (_i, [_vp, _u32, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _vp]),
+    "racc_host_scene_rebuild": (_i, [_vp, _u32, _vp, _u32, _vp, _u32, _P(_u32), _vp, _u32, _P(_u32), _vp, _u32, _P(_u32), _P(_u32)]),
     "racc_host_world_prepare": (_i, [_vp, _vp, _u32, _vp, _vp, _P(C.c_float), _vp, _u32, _P(_u32), _vp, _P(_u32)]),
     "racc_host_world_refit": (_i, [_vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _P(C.c_float), _vp]),
     "racc_host_world_rebuild": (_i, [_vp, _vp, _u32, _vp, _vp, _P(C.c_float), _vp, _u32, _P(_u32), _vp, _P(_u32)]),
@@ -341,6 +347,20 @@ def host_refit(blobs, vertices, indices):
     _check(load_library().racc_host_blobs_refit(_ptr(nodes), len(nodes), _ptr(pairs), len(pairs), int(blobs["pair_count"]), _ptr(remap), len(remap),
                                                 _ptr(v), len(v), _ptr(idx), idx.size, _ptr(out_nodes), _ptr(out_pairs)))
     return dict(nodes=out_nodes, pairs=out_pairs, remap=remap.copy(), pair_count=int(blobs["pair_count"]))
+
+
+def host_scene_rebuild(vertices, indices):
+    """racc_host_scene_rebuild: the specification of the device rebuild of a scene (no GPU needed) — the LBVH of racc_scene_rebuild_rule.h
+    over the triangles of the mesh (Morton keys of the triangle box centres, Karras's hierarchy; one triangle per pair, one pair per leaf).
+    Returns the reference-format blobs dict(nodes, pairs, remap, pair_count, height)."""
+    v = _as_verts4(vertices)
+    idx = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+    t = idx.size // 3
+    nodes, pairs, remap = np.zeros(max(t - 1, 1), GPU_NODE_DTYPE), np.zeros((t // 32 + 1) * 32, PAIR_DTYPE), np.zeros(2 * t + 2, np.uint32)
+    nn, npairs, nremap, height = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    _check(load_library().racc_host_scene_rebuild(_ptr(v), len(v), _ptr(idx), idx.size, _ptr(nodes), max(t - 1, 0), C.byref(nn), _ptr(pairs), len(pairs), C.byref(npairs),
+                                                  _ptr(remap), 2 * t, C.byref(nremap), C.byref(height)))
+    return dict(nodes=nodes[:nn.value].copy(), pairs=pairs[:npairs.value].copy(), remap=remap[:nremap.value].copy(), pair_count=t, height=int(height.value))
 
 
 NO_INSTANCE = 0xFFFFFFFF      # the instance index of a miss (racc_hip_world_intersect*)
@@ -556,6 +576,12 @@ class Refit:
         _check(load_library().racc_hip_refit_download(self._ctx._h, self._h, _ptr(nodes), len(nodes), _ptr(pairs), len(pairs)))
         return nodes, pairs
 
+    def download_remap(self):
+        """The scene's remap as the device holds it now (racc_hip_refit_download_remap): what a device rebuild wrote."""
+        remap = np.zeros(self._scene.info["remap_count"], np.uint32)
+        _check(load_library().racc_hip_refit_download_remap(self._ctx._h, self._h, _ptr(remap), len(remap)))
+        return remap
+
     def download_wide(self, format):
         """The scene's current 4-wide records of `format` (45: [N, 32] uint32 words, 50: [N, 16]), laid out as wide_nodes' are
         (racc_hip_refit_download_wide); the scene must carry that copy."""
@@ -572,6 +598,27 @@ class Refit:
         _check(load_library().racc_hip_refit_check(self._ctx._h, self._h, C.byref(n)))
         return int(n.value)
 
+    def rebuild(self, vertices):
+        """Host vertices ([V,3] or [V,4]), validated, blocking (racc_hip_scene_rebuild): a new tree over the mesh, built on the device.  Needs
+        a handle of Context.create_dynamic_scene.  The scene's info holds the real height afterwards."""
+        v = _as_verts4(vertices)
+        _check(load_library().racc_hip_scene_rebuild(self._ctx._h, self._h, _ptr(v), len(v)))
+        self._scene.refresh_info()
+
+    def rebuild_device(self, d_vertices, vertex_count, stream=None):
+        """Device-resident xyzw vertices as refit_device takes them, asynchronous on `stream` (racc_hip_scene_rebuild_device): the tree is
+        rebuilt in stream order.  The scene's info.inner_height is held at the rule's bound until check_rebuild()."""
+        _check(load_library().racc_hip_scene_rebuild_device(self._ctx._h, self._h, d_vertices, vertex_count, stream))
+        self._scene.refresh_info()
+
+    def check_rebuild(self):
+        """The height of the tree the scene holds now (racc_hip_scene_rebuild_check), which the scene's info takes over; synchronise the
+        rebuild's stream first."""
+        height = C.c_uint32(0)
+        _check(load_library().racc_hip_scene_rebuild_check(self._ctx._h, self._h, C.byref(height)))
+        self._scene.refresh_info()
+        return int(height.value)
+
     def destroy(self):
         if self._h:
             load_library().racc_hip_refit_destroy(self._ctx._h, self._h)
@@ -581,8 +628,12 @@ class Refit:
 class Scene:
     def __init__(self, ctx, handle):
         self._ctx, self._h = ctx, handle
+        self.refresh_info()
+
+    def refresh_info(self):
+        """racc_hip_scene_get_info again (a rebuild changes inner_height and spill_levels)."""
         info = SceneInfo()
-        _check(load_library().racc_hip_scene_get_info(handle, C.byref(info)))
+        _check(load_library().racc_hip_scene_get_info(self._h, C.byref(info)))
         self.info = {f: getattr(info, f) for f, _ in SceneInfo._fields_}
 
     def destroy(self):
@@ -693,6 +744,17 @@ class Context:
         create = load_library().racc_hip_refit_create_wide if wide else load_library().racc_hip_refit_create
         _check(create(self._h, scene._h, _ptr(idx), idx.size, int(vertex_count), C.byref(h)))
         return Refit(self, scene, h, vertex_count)
+
+    def create_dynamic_scene(self, vertices, indices):
+        """racc_hip_scene_rebuild_create: (Scene, Refit) — a scene whose tree is built, and can be rebuilt, on the device (the LBVH of
+        host_scene_rebuild), and its one handle: Refit.rebuild / rebuild_device / check_rebuild besides refit / refit_device / download.
+        Destroy the handle before the scene."""
+        v = _as_verts4(vertices)
+        idx = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+        hs, hr = C.c_void_p(), C.c_void_p()
+        _check(load_library().racc_hip_scene_rebuild_create(self._h, _ptr(v), len(v), _ptr(idx), idx.size, C.byref(hs), C.byref(hr)))
+        scene = Scene(self, hs)
+        return scene, Refit(self, scene, hr, len(v))
 
     def create_world(self, instances):
         """racc_hip_world_create: `instances` = a sequence of (transform [3,4] object-to-world, Scene) in instance-index order."""
